@@ -7,10 +7,15 @@ random legal positions per GPU, synthetic net). N > 1: every rank evaluates its 
 no data-path collective), weak scaling; value = all ranks' positions / max-over-ranks time.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 200 --warmup 20
 
-Rank 0 prints ONE JSON line. Extra objects:
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times exactly --steps steps and prints the headline (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the run's configuration and the per-kernel HIP-event times of
+the timed steps). --dump-outputs DIR writes the scores the timed path returned in its last step to DIR (see dump_outputs).
+Everything else - the CPU-oracle sample check, the N > 1 score gather, the roofline and the objects below - runs only with
+--full, after the timed region. Extra objects of a --full run:
   `roofline`      the dominant kernel - the column-sliced pipeline's gather (spx_ftx_gather_kernel; batches below 16 384
                   positions: spx_ft_kernel) - against the roof that BINDS it. The 100 MB of weight rows are resident in L2 /
                   Infinity Cache, so the gather is bound by the L2 -> CU path, not by HBM: `bound` = "l2", `achieved` = bytes
@@ -21,8 +26,8 @@ Rank 0 prints ONE JSON line. Extra objects:
   `wide_psq_rows` the same timed run on a context with SPX_CTX_WIDE_PSQ_ROWS (the one-kernel path, no 1 KiB u8 copies of
                   piece-square rows): every piece-square row fetched as its 2 KiB i16 row.
   `cpu_baseline`  the compiled reference (`oracle/_ref/sp_ref_probe_tame[_avx512]`) timed on a bounded sample of the same
-                  batch on this box's host cores. Its absence is an error (--allow-port-baseline times the scalar C
-                  restatement instead).
+                  batch on this box's host cores. Where it was not built (it needs the reference's sources), the scalar C
+                  restatement is timed instead and the record says so (kind 'port').
 Before the W warm-up steps the loop is additionally run untimed until the chip's clocks have settled (>= 1 s and three
 consecutive 10-step chunks within 2 %), so a short `--steps 20 --warmup 5` run measures the same steady state as a long one.
 """
@@ -165,12 +170,13 @@ def cpu_baseline(sp, positions, blob, seconds, allow_port=False):
     except (OSError, StopIteration):
         pass
     cores = usable_cpus()
-    if not os.path.exists(probe) and not allow_port:
-        raise SystemExit(f"bench.py: {probe} is missing - the cpu_baseline leg times the COMPILED REFERENCE, which is built "
-                         "in the authoring container (`make -C oracle ref ref512`, needs /root/reference) and travels "
-                         "untracked in oracle/_ref/. Re-run with --allow-port-baseline to time the scalar C restatement "
-                         "(kind 'port', 1 thread) instead, or with --no-cpu-baseline.")
-    if os.path.exists(probe):
+    missing = None
+    if not os.path.exists(probe):
+        # (build() compiles the probe only where the reference's sources are; a checkout without them times the port)
+        missing = (f"{os.path.relpath(probe, ROOT)} was not built (`make -C oracle ref ref512` needs the reference's "
+                   "sources): the scalar C restatement is timed instead")
+        print(f"[bench] cpu_baseline: {missing}", file=sys.stderr)
+    else:
         try:
             cmds = "".join(f"add {sp.position_to_fen(p)}\n" for p in sample)
             cmds += f"bench {cores} {seconds}\nquit\n"
@@ -201,8 +207,33 @@ def cpu_baseline(sp, positions, blob, seconds, allow_port=False):
         oracle.spxo_eval_mailboxes(mail.ctypes.data, stm.ctypes.data, len(sample), out.ctypes.data)
         done += len(sample)
     dt = time.perf_counter() - t0
-    return {"value": done / dt, "unit": "evals/s", "cores": 1, "kind": "port",
-            "sample": f"scalar C restatement (oracle/spx_oracle.c) over the first {len(sample)} positions, {dt:.1f} s, 1 thread"}
+    rec = {"value": done / dt, "unit": "evals/s", "cores": 1, "kind": "port",
+           "sample": f"scalar C restatement (oracle/spx_oracle.c) over the first {len(sample)} positions, {dt:.1f} s, 1 thread"}
+    if missing:
+        rec["note"] = missing
+    return rec
+
+
+DUMP_LIMIT_BYTES = 60 << 20  # all files of one --dump-outputs run together: below 64 MB, .npy headers included
+
+
+def dump_outputs(directory, name, d_scores, rank, world):
+    """--dump-outputs: the int32 scores the timed path returned in its last step, as float64 (exact for every int32), to
+    DIR/<name>.npy (N > 1: DIR/<name>_rank<r>.npy, one file per rank's shard). An output above its share of DUMP_LIMIT_BYTES is
+    written as a fixed sample - the sorted distinct positions of a seeded draw - with those positions' indices beside it in
+    DIR/<name>_index.npy (float64 too), so that two builds given the same arguments can be compared value for value."""
+    os.makedirs(directory, exist_ok=True)
+    tag = name if world == 1 else f"{name}_rank{rank}"
+    n, budget = d_scores.numel(), DUMP_LIMIT_BYTES // world
+    if 8 * n <= budget:
+        np.save(os.path.join(directory, f"{tag}.npy"), d_scores.cpu().numpy().astype(np.float64))
+        return
+    idx = np.unique(np.random.default_rng(20260927).integers(0, n, size=budget // 16))
+    import torch
+
+    picked = d_scores[torch.from_numpy(idx).to(d_scores.device)].cpu().numpy()
+    np.save(os.path.join(directory, f"{tag}.npy"), picked.astype(np.float64))
+    np.save(os.path.join(directory, f"{tag}_index.npy"), idx.astype(np.float64))
 
 
 def delta_rows_sample(sp, parents, children, sample=256):
@@ -282,16 +313,34 @@ def incremental_bench(args, sp, torch, group, rank, local_rank, world):
     sync()
     elapsed = group.max_float(time.perf_counter() - t0)
     _, update_ms, mlp_ms, calls = state.profile_end()
+    d_last = d_outs[(step_no[0] - 1) & 1]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "evals", d_last, rank, world)
+    line = {
+        "metric": "nnue_incremental_updates_per_sec", "value": world * G * args.steps / elapsed, "unit": "updates+evals/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "i16 accumulate / i8 MFMA L1 / i32 tail", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[2]/[3] shape: per step one ply of incremental accumulator updates "
+                               "(device-derived add/sub deltas) + evaluation for every one of the concurrent games",
+                   "games_per_gpu": G, "settle_steps": settle_steps,
+                   "issue": ("pipelined spx_acc_update_eval_device_async: update kernels in call order, sort + MLP of a "
+                             "ply beside the next ply's update kernel" if pipelined else "stream-ordered calls")},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        group.close()
+        return
     # parity inside the bench: the incrementally maintained evals equal a full refresh of the final boards
     full = torch.empty(G, dtype=torch.int32, device="cuda")
     state.evaluate_once_device(d_boards[board_index(step_no[0])].data_ptr(), G, full.data_ptr(), stream)
     torch.cuda.synchronize()
-    exact = group.sum_int(int(torch.equal(full, d_outs[(step_no[0] - 1) & 1]))) == world
+    exact = group.sum_int(int(torch.equal(full, d_last))) == world
     if rank == 0:
         psq_d, thr_d = delta_rows_sample(sp, chain[3], chain[4])
         compulsory = 2 * 4096 + 72  # parent accumulators read + child accumulators written + the two records
         update_s = update_ms / max(calls, 1) / 1e3
-        value = world * G * args.steps / elapsed
         pmc = load_pmc("incremental", batch=G, preset=args.preset)
         kp = kernel_pmc(pmc, "spx_update_kernel<")
         roofline = {
@@ -316,19 +365,9 @@ def incremental_bench(args, sp, torch, group, rank, local_rank, world):
             roofline["traffic_over_achievable"] = roofline["traffic_gbs"] / HBM_ACHIEVABLE_GBS  # the binding path
         if pmc:
             roofline["valu"] = valu_block(kp, pmc.get("valu_cycles_per_wave_instr", 4))
-        print(json.dumps({
-            "metric": "nnue_incremental_updates_per_sec", "value": value, "unit": "updates+evals/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "i16 accumulate / i8 MFMA L1 / i32 tail", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]/[3] shape: per step one ply of incremental accumulator updates "
-                                   "(device-derived add/sub deltas) + evaluation for every one of the concurrent games",
-                       "games_per_gpu": G, "bit_exact_vs_full_refresh": bool(exact), "settle_steps": settle_steps,
-                       "issue": ("pipelined spx_acc_update_eval_device_async: update kernels in call order, sort + MLP of a "
-                                 "ply beside the next ply's update kernel" if pipelined else "stream-ordered calls"),
-                       "mean_delta_rows_per_update": {"psq": psq_d, "threat": thr_d}},
-            "roofline": roofline,
-        }), flush=True)
+        line["config"].update(bit_exact_vs_full_refresh=bool(exact), mean_delta_rows_per_update={"psq": psq_d, "threat": thr_d})
+        line["roofline"] = roofline
+        print(json.dumps(line), flush=True)
     group.close()
 
 
@@ -805,27 +844,37 @@ def main():
                          "uniform move choice kernels) instead of the host chess core - for nodes whose ranks share few CPUs")
     ap.add_argument("--host-positions", action="store_true",
                     help="N > 1 generates positions on the device by default; this keeps the host chess core (8 s per rank)")
-    ap.add_argument("--no-gather", action="store_true", help="N > 1 all-gathers the last step's scores by default; skip it")
+    ap.add_argument("--no-gather", action="store_true", help="N > 1 --full runs all-gather the last step's scores by default; skip it")
     ap.add_argument("--no-settle", action="store_true", help="skip the time-based clock warm-up before the W warm-up steps")
     ap.add_argument("--no-wide", action="store_true", help="skip the second timed run with SPX_CTX_WIDE_PSQ_ROWS")
     ap.add_argument("--gather", action="store_true",
-                    help="N > 1: all_gather the per-rank scores of the last step (RCCL) and check the gathered array "
+                    help="with --full, N > 1: all_gather the per-rank scores of the last step (RCCL) and check the gathered array "
                          "against each rank's own shard checksum (SURVEY 8e's optional result gather; outside the timed region)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary legs (incremental ply, config-3 replays, self-play, realistic-weights net, gather ceiling) that "
-                         "the single-GPU run appends to the JSON line after the headline's timed region")
+                         "a --full run appends to the JSON line after the headline's timed region")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--allow-port-baseline", action="store_true",
-                    help="time the scalar C restatement when the compiled reference probe (oracle/_ref) is missing, "
-                         "instead of failing")
+                    help="time the scalar C restatement when the compiled reference probe (oracle/_ref) fails, instead of "
+                         "failing (a probe that was not built is always replaced by the restatement)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed region, also run the checks and the other measurements: the CPU-oracle "
+                         "sample check, the N > 1 score gather, roofline and PMC figures, the wide-row run, the secondary legs "
+                         "and the CPU baseline (the --no-* options above narrow what --full adds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores the timed path returned in its last step to DIR/*.npy (float64, <= 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.gather and not args.full:
+        ap.error("--gather is one of the checks of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
-    if args.gpus > 1:  # ranks of a node share few host CPUs and the point of the run is RCCL: both default on
+    if args.gpus > 1:  # ranks of a node share few host CPUs and the point of a --full run is RCCL: both default on
         args.device_positions = not args.host_positions
-        args.gather = not args.no_gather
+        args.gather = args.full and not args.no_gather
 
     import torch
 
@@ -890,6 +939,63 @@ def main():
     # checksum of checksums over all shards (summed in slabs: no 8-byte copy of an HBM-filling score array)
     checksum = group.sum_int(sum(int(d_last[lo:lo + (1 << 26)].sum(dtype=torch.int64).item())
                                  for lo in range(0, args.batch, 1 << 26)))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "scores", d_last, rank, world)
+
+    sliced = state.takes_sliced_pipeline(min(args.batch, state.scratch_batch), pipelined=pipelined)
+    line = {
+        "metric": "nnue_position_evals_per_sec",
+        "value": world * args.batch * args.steps / elapsed,
+        "unit": "evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "i16 accumulate / i8 MFMA L1 / i32 tail",
+        "data": "synthetic",
+        "config": {
+            "workload": (f"BASELINE configs[1]: full-refresh NNUE forward on {args.batch} seeded random legal positions "
+                         "per GPU (random playouts 8-120 plies, every 4th game DFRC"
+                         + (", generated on the device" if args.device_positions else "") + ")"
+                         + (", bit-exact vs CPU" if args.full else "")
+                         + (f"; batch tiled from {n_distinct} distinct positions" if n_distinct < args.batch else "")),
+            "batch_per_gpu": args.batch,
+            "resident_bytes": int(torch.cuda.max_memory_allocated()) if hasattr(torch.cuda, "max_memory_allocated") else None,
+            "chunks_per_step": -(-args.batch // state.scratch_batch),
+            "net": (f"file {os.path.basename(args.net)} '{net.name}'" if args.net else
+                    f"synthetic CBNF '{net.name}' (Stormphrax 8.0.2 shape: (704x16+64368)->1024)x2->(32x2->64->1)x8"),
+            "compact_psq_rows": f"{state.compact_psq_rows} of 11264 piece-square rows fit i8 and are served as 1 KiB copies"
+                                + (f"; {state.near_psq_rows} more have <= 32 weights outside i8: 1 KiB copy + exact remainders"
+                                   if state.near_psq_rows else ""),
+            "parallelism": f"positions sharded over {world} GPU(s), no collective on the data path; "
+                           + ("steps issued through the pipelined spx_eval_full_device_async (two internal streams: "
+                              "sorts / MLP of a batch overlap the next batch's feature-transformer kernel)"
+                              if pipelined else "steps issued stream-ordered on one HIP stream per GPU"),
+            "ranks": {"backend": seen_backend, "world": seen_world,
+                      "ft_kernel_ms_per_rank": rank_ft_ms,
+                      "evals_per_sec_per_rank_kernel_bound": {
+                          "min": args.batch / (max(rank_ft_ms) / 1e3), "max": args.batch / (min(rank_ft_ms) / 1e3),
+                          "mean": args.batch / (sum(rank_ft_ms) / len(rank_ft_ms) / 1e3)},
+                      "note": "per-rank figures are each rank's own FT-kernel HIP-event time (rank order): a straggler "
+                              "GPU shows here; `value` uses the MAX-over-ranks wall time"},
+            "net_distribution": (f"rank 0's {blob.size} B net image broadcast to the other ranks over "
+                                 f"{backend} in {net_bcast_s * 1e3:.1f} ms (init only)" if world > 1 else "single rank"),
+            "settle_steps": settle_steps,
+            "checksum": checksum,
+            "kernel_ms": {"sort": sort_ms / max(calls, 1), "before_ft": timed_prepare_ms, "ft": ft_ms / max(calls, 1),
+                          "mlp": mlp_ms / max(calls, 1)},
+            "full_refresh_path": ("column-sliced pipeline (spx_ftx.hip): extraction, counting sort, plan, gather" if sliced
+                                  else "one kernel (spx_ft_kernel)"),
+        },
+    }
+    if not args.full:  # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        group.close()
+        return
 
     # ---- parity inside the bench (outside the timed region): oracle on a sample of every rank's shard ----
     n_sample = min(4096, n_distinct)
@@ -934,9 +1040,7 @@ def main():
         algo_bytes = 2048 * psq_rows + 1024 * thr_rows + 36 * args.batch  # per launch
         requested = 2048 * wide_rows + 1024 * (compact_rows + thr_rows) + 36 * args.batch  # what the loads ask for
         ft_avg_s = ft_ms / max(calls, 1) / 1e3
-        value = world * args.batch * args.steps / elapsed
         pmc = load_pmc("full", batch=args.batch, preset=args.preset, net=args.net) if n_distinct == args.batch else None
-        sliced = state.takes_sliced_pipeline(min(args.batch, state.scratch_batch), pipelined=pipelined)
         kp = kernel_pmc(pmc, "spx_ftx_gather_kernel" if sliced else "spx_ft_kernel")
         hbm = {
             "algorithmic_bytes_per_launch": algo_bytes, "bytes_per_position": algo_bytes / args.batch,
@@ -1078,58 +1182,13 @@ def main():
                                    "mfma_busy_frac": kp["counters"].get("SQ_VALU_MFMA_BUSY_CYCLES", 0) / (N_SIMDS * cyc),
                                    "note": "TCP_TOTAL_CACHE_ACCESSES / (256 CUs x kernel cycles) from the committed PMC passes (the "
                                            "kernel alone: rocprofv3 serialises the dispatches it counts)"}
-        line = {
-            "metric": "nnue_position_evals_per_sec",
-            "value": value,
-            "unit": "evals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "i16 accumulate / i8 MFMA L1 / i32 tail",
-            "data": "synthetic",
-            "bit_exact_sample": bool(exact),
-            "config": {
-                "workload": (f"BASELINE configs[1]: full-refresh NNUE forward on {args.batch} seeded random legal positions "
-                             "per GPU (random playouts 8-120 plies, every 4th game DFRC"
-                             + (", generated on the device" if args.device_positions else "") + "), bit-exact vs CPU"
-                             + (f"; batch tiled from {n_distinct} distinct positions" if n_distinct < args.batch else "")),
-                "batch_per_gpu": args.batch,
-                "resident_bytes": int(torch.cuda.max_memory_allocated()) if hasattr(torch.cuda, "max_memory_allocated") else None,
-                "chunks_per_step": -(-args.batch // state.scratch_batch),
-                "net": (f"file {os.path.basename(args.net)} '{net.name}'" if args.net else
-                        f"synthetic CBNF '{net.name}' (Stormphrax 8.0.2 shape: (704x16+64368)->1024)x2->(32x2->64->1)x8"),
-                "compact_psq_rows": f"{state.compact_psq_rows} of 11264 piece-square rows fit i8 and are served as 1 KiB copies"
-                                    + (f"; {state.near_psq_rows} more have <= 32 weights outside i8: 1 KiB copy + exact remainders"
-                                       if state.near_psq_rows else ""),
-                "parallelism": f"positions sharded over {world} GPU(s), no collective on the data path; "
-                               + ("steps issued through the pipelined spx_eval_full_device_async (two internal streams: "
-                                  "sorts / MLP of a batch overlap the next batch's feature-transformer kernel)"
-                                  if pipelined else "steps issued stream-ordered on one HIP stream per GPU"),
-                "ranks": {"backend": seen_backend, "world": seen_world,
-                          "ft_kernel_ms_per_rank": rank_ft_ms,
-                          "evals_per_sec_per_rank_kernel_bound": {
-                              "min": args.batch / (max(rank_ft_ms) / 1e3), "max": args.batch / (min(rank_ft_ms) / 1e3),
-                              "mean": args.batch / (sum(rank_ft_ms) / len(rank_ft_ms) / 1e3)},
-                          "note": "per-rank figures are each rank's own FT-kernel HIP-event time (rank order): a straggler "
-                                  "GPU shows here; `value` uses the MAX-over-ranks wall time"},
-                "net_distribution": (f"rank 0's {blob.size} B net image broadcast to the other ranks over "
-                                     f"{backend} in {net_bcast_s * 1e3:.1f} ms (init only)" if world > 1 else "single rank"),
-                "settle_steps": settle_steps,
-                "bit_exact_sample": f"{n_sample} positions of every rank's shard checked against the CPU oracle "
-                                    "(oracle/spx_oracle.c) after the timed region",
-                "gathered_scores_ok": gathered_ok,
-                "checksum": checksum,
-                "kernel_ms": {"sort": sort_ms / max(calls, 1), "before_ft": timed_prepare_ms, "ft": ft_ms / max(calls, 1),
-                              "mlp": mlp_ms / max(calls, 1)},
-                "full_refresh_path": ("column-sliced pipeline (spx_ftx.hip): extraction, counting sort, plan, gather" if sliced
-                                      else "one kernel (spx_ft_kernel)"),
-            },
-            "roofline": roofline,
-        }
+        line["bit_exact_sample"] = bool(exact)
+        line["config"].update({
+            "bit_exact_sample": f"{n_sample} positions of every rank's shard checked against the CPU oracle "
+                                "(oracle/spx_oracle.c) after the timed region",
+            "gathered_scores_ok": gathered_ok,
+        })
+        line["roofline"] = roofline
         if wide:
             line["wide_psq_rows"] = wide
         if secondary:

@@ -6,6 +6,7 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,6 +106,43 @@ def test_bench_refuses_to_run_without_a_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"],
                          capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and "needs a GPU" in (out.stderr + out.stdout)
+
+
+def test_bench_refuses_arguments_it_cannot_honour():
+    """--steps sets the number of timed steps (at least one); the score gather is one of --full's checks."""
+    import subprocess
+    import sys
+
+    for extra in (["--steps", "0"], ["--warmup", "-1"], ["--gather"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 2 and "error:" in out.stderr, (extra, out.stderr)
+
+
+def test_bench_dump_outputs_stays_within_its_size_limit(tmp_path):
+    """bench.py --dump-outputs: float64 scores, the whole output while it fits the limit, else a fixed seeded sample with the
+    sampled positions' indices beside it; the same scores give the same files."""
+    import subprocess
+    import sys
+
+    script = (
+        "import sys, torch, bench\n"
+        "bench.DUMP_LIMIT_BYTES = 4096\n"
+        "d = sys.argv[1]\n"
+        "bench.dump_outputs(d + '/small', 'scores', torch.arange(-256, 256, dtype=torch.int32), 0, 1)\n"
+        "for run in ('a', 'b'):\n"
+        "    bench.dump_outputs(d + '/' + run, 'scores', torch.arange(100000, dtype=torch.int32) * 7 - 5, 0, 1)\n"
+        "bench.dump_outputs(d + '/ranks', 'scores', torch.arange(100000, dtype=torch.int32), 1, 2)\n")
+    subprocess.check_call([sys.executable, "-c", script, str(tmp_path)], cwd=ROOT, timeout=300)
+    small = np.load(tmp_path / "small" / "scores.npy")
+    assert small.dtype == np.float64 and np.array_equal(small, np.arange(-256, 256))
+    assert sorted(os.listdir(tmp_path / "a")) == ["scores.npy", "scores_index.npy"]
+    scores, index = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "scores_index.npy")
+    assert scores.dtype == index.dtype == np.float64 and 0 < scores.size == index.size <= 4096 // 16
+    assert np.all(np.diff(index) > 0) and np.array_equal(scores, index * 7 - 5)
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= 4096
+    assert np.array_equal(scores, np.load(tmp_path / "b" / "scores.npy"))
+    assert sorted(os.listdir(tmp_path / "ranks")) == ["scores_rank1.npy", "scores_rank1_index.npy"]
+    assert np.load(tmp_path / "ranks" / "scores_rank1.npy").size <= 4096 // 2 // 16
 
 
 def test_cpp_mirror_reports_the_missing_device_as_an_exception(tmp_path):

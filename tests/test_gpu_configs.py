@@ -79,7 +79,7 @@ def test_two_rank_control_flow_on_one_gpu(script, tmp_path):
                 "127.0.0.1", "--master-port", str(free_port())]
     if script == "bench":
         cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--batch", "16384",
-                          "--gather", "--no-wide"]
+                          "--full", "--gather", "--no-wide"]
     else:
         cmd = launcher + [os.path.join(ROOT, "tools", "spx_selfplay.py"), "--games", "512", "--target", "700", "--dfrc",
                           "--out", str(tmp_path / "sp")]
@@ -105,11 +105,11 @@ def test_two_rank_control_flow_on_one_gpu(script, tmp_path):
 
 def test_bare_bench_command_launches_its_own_ranks():
     """`python bench.py --gpus 2 ...` with no launcher and no WORLD_SIZE (the shape of the driver's N = 1 command) starts its
-    two ranks itself; N > 1 defaults to device-generated positions and the score gather."""
+    two ranks itself; N > 1 defaults to device-generated positions and, with --full, the score gather."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SPX_BENCH_SHARE_GPU="1", SPX_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                          "--batch", "16384", "--no-wide", "--no-secondary"], env=env, cwd=ROOT, capture_output=True, text=True,
+                          "--batch", "16384", "--full", "--no-wide", "--no-secondary"], env=env, cwd=ROOT, capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "launching 2 ranks" in out.stderr
@@ -128,7 +128,7 @@ def test_every_collective_once_through_rccl(tmp_path):
     on device tensors, in bench.py and in the self-play tool."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SPX_FORCE_DIST="1", MASTER_PORT="29641")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--gather",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--gather",
                           "--device-positions", "--no-wide", "--no-secondary", "--no-cpu-baseline"], env=env, cwd=ROOT,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -141,6 +141,28 @@ def test_every_collective_once_through_rccl(tmp_path):
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["collectives"] == "nccl" and line["games"] == 300 and os.path.getsize(str(tmp_path / "g.0.vf")) > 0
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_its_scores(sp, net_blob, oracle, tmp_path):
+    """A plain bench run (no --full) prints the headline of exactly --steps timed steps and nothing beyond it; --dump-outputs
+    writes the last step's scores, which are the CPU oracle's for the bench's seeded positions."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                          "--batch", "16384", "--dump-outputs", str(tmp_path / "dump")], cwd=ROOT, capture_output=True,
+                         text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["metric"] == "nnue_position_evals_per_sec" and line["unit"] == "evals/s" and line["higher_is_better"] is True
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 16384 / (line["ms_per_step"] / 1e3)) < 1e-6 * line["value"]
+    assert not {"roofline", "cpu_baseline", "secondary", "wide_psq_rows", "bit_exact_sample"} & set(line)
+    assert os.listdir(tmp_path / "dump") == ["scores.npy"]
+    scores = np.load(tmp_path / "dump" / "scores.npy")
+    assert scores.dtype == np.float64 and scores.shape == (16384,)
+    assert int(scores.sum()) == line["config"]["checksum"]
+    pos = sp.random_positions(16384, seed=20260927, min_ply=8, max_ply=120, dfrc_every=4)
+    oracle.use(net_blob("tame"), "tame")
+    mail, stm = sp.positions_to_mailboxes(pos[::16])
+    assert np.array_equal(scores[::16].astype(np.int32), oracle.eval_mailboxes(mail, stm))
 
 
 def test_device_group_shards_a_batch_over_its_members(sp, net_blob, oracle):

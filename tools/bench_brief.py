@@ -17,7 +17,7 @@ if label == "-" or (label and os.path.exists(label)):
     print(f"{label:28s} {j['value']:.4e} {j.get('unit', '')}  {j['ms_per_step']:.4f} ms/step  sort {k['sort']:.4f} ft {k['ft']:.4f} mlp {k['mlp']:.4f}  "
           f"exact {j.get('bit_exact_sample', j.get('config', {}).get('bit_exact_sample'))}")
     raise SystemExit(0)
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary", "--no-wide"] + sys.argv[2:],
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary", "--no-wide"] + sys.argv[2:],
                      capture_output=True, text=True)
 try:
     j = json.loads(out.stdout.strip().splitlines()[-1])

@@ -16,14 +16,14 @@ cp $REPO/gpurun_out/pmc_inc_$TAG/pmc.json $OUT/pmc_incremental.json
 rm -rf $REPO/gpurun_out/prof_$TAG $REPO/gpurun_out/pmc_inc_$TAG
 [ -s $OUT/pmc_full_refresh.json ] && cp $OUT/pmc_full_refresh.json $REPO/profiles/${TAG}_pmc_full_refresh.json
 [ -s $OUT/pmc_incremental.json ] && cp $OUT/pmc_incremental.json $REPO/profiles/${TAG}_pmc_incremental.json
-( time python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err ) 2> $OUT/bench_n1_wall_time.txt
-python bench.py --steps 20 --warmup 5 > $OUT/bench_n1_driver_args.json 2> $OUT/bench_driver.err
-python bench.py --no-pipeline --no-cpu-baseline > $OUT/bench_n1_strict_stream_order.json 2> $OUT/bench_strict.err
-python bench.py --device-positions --no-cpu-baseline --no-wide > $OUT/bench_n1_device_positions.json 2> $OUT/bench_devpos.err
-python bench.py --mode incremental --no-cpu-baseline > $OUT/bench_incremental_n1.json 2> $OUT/bench_incremental_n1.err
-python bench.py --mode incremental --no-pipeline --no-cpu-baseline > $OUT/bench_incremental_n1_strict_stream_order.json 2>> $OUT/bench_incremental_n1.err
-python bench.py --mode incremental --batch 262144 --steps 100 --no-cpu-baseline > $OUT/bench_incremental_n1_262144.json 2>> $OUT/bench_incremental_n1.err
-python bench.py --batch 4194304 --steps 20 --warmup 3 --no-cpu-baseline --no-wide > $OUT/bench_n1_batch4M.json 2> $OUT/bench_4m.err
+( time python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err ) 2> $OUT/bench_n1_wall_time.txt
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_n1_driver_args.json 2> $OUT/bench_driver.err
+python bench.py --full --no-pipeline --no-cpu-baseline > $OUT/bench_n1_strict_stream_order.json 2> $OUT/bench_strict.err
+python bench.py --full --device-positions --no-cpu-baseline --no-wide > $OUT/bench_n1_device_positions.json 2> $OUT/bench_devpos.err
+python bench.py --full --mode incremental --no-cpu-baseline > $OUT/bench_incremental_n1.json 2> $OUT/bench_incremental_n1.err
+python bench.py --full --mode incremental --no-pipeline --no-cpu-baseline > $OUT/bench_incremental_n1_strict_stream_order.json 2>> $OUT/bench_incremental_n1.err
+python bench.py --full --mode incremental --batch 262144 --steps 100 --no-cpu-baseline > $OUT/bench_incremental_n1_262144.json 2>> $OUT/bench_incremental_n1.err
+python bench.py --full --batch 4194304 --steps 20 --warmup 3 --no-cpu-baseline --no-wide > $OUT/bench_n1_batch4M.json 2> $OUT/bench_4m.err
 python tools/gpu_measure.py > $OUT/secondary.json 2> $OUT/secondary.err
 python tools/spx_selfplay.py --games 4096 --target 8192 --dfrc > $OUT/selfplay_4096.json 2> $OUT/selfplay.err
 python tools/spx_selfplay.py --games 4096 --target 65536 --dfrc > $OUT/selfplay_4096_long.json 2>> $OUT/selfplay.err
@@ -62,7 +62,7 @@ PY
 rm -rf $OUT/sp_pmc_*
 # round 4: the N > 1 line's new legs (two ranks sharing this GPU over gloo: control flow, not a scaling number), BASELINE configs[4],
 # the column-sliced pipeline's kernels, the reference engine on the GPU evaluator
-SPX_BENCH_SHARE_GPU=1 SPX_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 5 --no-wide > $OUT/bench_n2_two_ranks_sharing_one_gpu.json 2> $OUT/bench_n2.err
+SPX_BENCH_SHARE_GPU=1 SPX_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-wide > $OUT/bench_n2_two_ranks_sharing_one_gpu.json 2> $OUT/bench_n2.err
 python tests/_config5_worker.py > $OUT/config5.log 2>&1 && cp $REPO/gpurun_out/config5_hbm_filling.json $OUT/bench_n1_config5_hbm_filling.json
 bash tools/gpu_kstats.sh sliced_$TAG --no-pipeline > $OUT/kstats_sliced_pipeline_stream_ordered.txt 2>&1
 SPX_OPTIONS=ftx=0 bash tools/gpu_kstats.sh onekernel_$TAG --no-pipeline > $OUT/kstats_one_kernel_path_stream_ordered.txt 2>&1
