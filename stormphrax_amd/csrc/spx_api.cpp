@@ -51,11 +51,13 @@ constexpr size_t kProfEventsPerCall = 5;
 
 // scratch of the column-sliced full refresh (spx_ftx.hip): one set per context and per lane, allocated on first use
 struct FtxScratch {
-    uint32_t *lists = nullptr, *heads = nullptr, *ranks = nullptr, *hist = nullptr, *binStart = nullptr,
+    uint16_t* lists = nullptr;
+    uint32_t *heads = nullptr, *ranks = nullptr, *hist = nullptr, *binStart = nullptr,
              *sorted = nullptr, *plan = nullptr, *groupHead = nullptr, *stages = nullptr, *outHist = nullptr;
     size_t capacity = 0;  // positions per pass
     void release() {
-        for (uint32_t* q : {lists, heads, ranks, hist, binStart, sorted, plan, groupHead, stages, outHist}) {
+        if (lists) (void)hipFree(lists);
+        for (uint32_t* q : {heads, ranks, hist, binStart, sorted, plan, groupHead, stages, outHist}) {
             if (q) (void)hipFree(q);
         }
         *this = FtxScratch{};
@@ -940,10 +942,10 @@ static int runTinyMlp(spx_ctx* ctx, const void* d_records, size_t n, void* d_out
 
 // ---- the gather's hot set ----
 // the tables of a chosen set: row -> slot map, the rows' slices in slot order. The caller guarantees that no gather of this context is
-// in flight (lists hold LDS offsets of the set they were extracted under).
+// in flight (lists hold LDS rows of the set they were extracted under).
 static int installHotRows(spx_ctx* ctx, const std::vector<uint32_t>& ids, hipStream_t s) {
     const uint32_t n = uint32_t(std::min<size_t>(ids.size(), kFtxHotRowsMax));
-    // no gather of this context may be in flight: lists hold LDS offsets of the set they were extracted under
+    // no gather of this context may be in flight: lists hold LDS rows of the set they were extracted under
     SPX_HIP(hipStreamSynchronize(ctx->stream));
     for (auto& lane : ctx->lanes) {
         if (lane.stream) SPX_HIP(hipStreamSynchronize(lane.stream));
@@ -1056,7 +1058,7 @@ static bool ensureFtx(spx_ctx* ctx, FtxScratch& x, size_t passPositions, hipStre
     // (option ftx_fail_after = k, tests only: the k-th scratch set "does not fit" - what a context sized to fill the HBM runs into)
     if (ctx->ftxFailAfter >= 0 && ctx->ftxScratchSets++ >= ctx->ftxFailAfter) return fail();
     const size_t cap = std::min(ctx->maxBatch, kFtxMaxPositions);
-    auto alloc = [&](uint32_t*& ptr, size_t bytes) { return hipMalloc(reinterpret_cast<void**>(&ptr), bytes) == hipSuccess; };
+    auto alloc = [&](auto*& ptr, size_t bytes) { return hipMalloc(reinterpret_cast<void**>(&ptr), bytes) == hipSuccess; };
     if (!alloc(x.lists, ftxListBytes(cap)) || !alloc(x.heads, 2 * cap * 16) ||
         !alloc(x.ranks, 2 * cap * 4) || !alloc(x.hist, kFtxBins * 4) || !alloc(x.binStart, (kFtxBins + 17 + 8) * 4) ||
         !alloc(x.outHist, (kHistOut + 16) * 4) ||
@@ -2519,35 +2521,36 @@ int spx_debug_ftx_lists(spx_ctx* ctx, int slot, size_t n, uint32_t* counts, uint
     }
     SPX_HIP(hipSetDevice(ctx->device));
     SPX_HIP(hipDeviceSynchronize());
-    std::vector<uint32_t> lists(2 * n * kFtxListStride), heads(2 * n * 4);
-    SPX_HIP(hipMemcpy(lists.data(), x.lists, lists.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint16_t> lists(2 * n * kFtxListStride);
+    std::vector<uint32_t> heads(2 * n * 4);
+    SPX_HIP(hipMemcpy(lists.data(), x.lists, lists.size() * 2, hipMemcpyDeviceToHost));
     SPX_HIP(hipMemcpy(heads.data(), x.heads, heads.size() * 4, hipMemcpyDeviceToHost));
     for (size_t q = 0; q < 2 * n; ++q) {
         const uint32_t head = heads[4 * q], bucket = heads[4 * q + 2] / kFtxQuartetBins;
         const uint32_t nHi = head & 0x3Fu, nLds = (head >> 6) & 0x1FFu, nCold = (head >> 15) & 0x1FFu;
-        const uint32_t* list = lists.data() + q * kFtxListStride;
+        const uint16_t* list = lists.data() + q * kFtxListStride;
         uint32_t* out = rows + q * kFtxListStride;
         uint32_t nPsq = 0, nThr = 0, k = 0;
-        for (uint32_t i = 0; i < nLds; ++i) {  // piece-square rows first, then the hot rows
-            const uint32_t off = list[kFtxListLds + i];
-            if (off < kFtxSlabBytes) {
-                out[k++] = bucket * kFtxSlabRows + off / 128;
+        for (uint32_t i = 0; i < nLds; ++i) {  // piece-square rows (slab rows) first, then the hot rows (705 + slot)
+            const uint32_t r = list[kFtxListLds + i];
+            if (r < kFtxSlabRows) {
+                out[k++] = bucket * kFtxSlabRows + r;
                 ++nPsq;
             }
         }
         for (uint32_t i = 0; i < nLds; ++i) {
-            const uint32_t off = list[kFtxListLds + i];
-            if (off >= kFtxSlabBytes) {
-                const uint32_t hot = (off - kFtxSlabBytes) / 128;
+            const uint32_t r = list[kFtxListLds + i];
+            if (r > kFtxSlabRows) {
+                const uint32_t hot = r - (kFtxSlabRows + 1);
                 out[k++] = hot < ctx->hotIds.size() ? ctx->hotIds[hot] : 0xFFFFFFFFu;
                 ++nThr;
             }
         }
         for (uint32_t i = 0; i < nCold; ++i) {
-            out[k++] = list[kFtxListCold + i] / 128;
+            out[k++] = list[kFtxListCold + i];
             ++nThr;
         }
-        for (uint32_t i = 0; i < nHi; ++i) out[k++] = list[kFtxListHi + i] / 128 - kFtxPsqHiBase;
+        for (uint32_t i = 0; i < nHi; ++i) out[k++] = list[kFtxListHi + i];
         counts[3 * q] = nPsq, counts[3 * q + 1] = nThr, counts[3 * q + 2] = nHi;
     }
     return SPX_OK;

@@ -48,10 +48,11 @@ constexpr uint32_t kFtxHotRowsDefault = 256;   // slab 88.1 + hot 32 + ring 16 =
 constexpr uint32_t kFtxHotHashWords = 1024;    // the extraction's LDS copy of the set: 256 buckets x 4 entries
 constexpr uint32_t kFtxRingBytesPerWave = 1024 + 64;  // one stage (16 steps x 8 perspectives x 4 entries of 16 bits; high-byte planes: 8 steps of 32-bit entries) + the group's head
 
-// ---- per-perspective lists written by the extraction pass: [perspective][kFtxListStride] words ----
-// [0, 288) the LDS section: the piece-square rows ((row - 704 bucket) * 128, into the slab), then the HOT threat / pawn-pair rows
-// (kFtxSlabBytes + slot * 128) - byte offsets into the gather's LDS; [288, 320) high-byte planes of the wide piece-square rows and
-// [320, 576) the COLD threat / pawn-pair rows as slice offsets (row index * 128). Words behind a section's count are undefined.
+// ---- per-perspective lists written by the extraction pass: [perspective][kFtxListStride] 16-bit row indices ----
+// [0, 288) the LDS section, in the numbering of the gather's LDS: the piece-square rows (row - 704 bucket: slab row), then the HOT
+// threat / pawn-pair rows (705 + slot); [288, 320) the wide piece-square rows whose high-byte plane is fetched (piece-square row
+// index) and [320, 576) the COLD threat / pawn-pair rows (threat row index). Entries behind a section's count are undefined.
+// (Round 7: 16-bit entries, the numbering the pack kernel writes into the walk - half the extraction's stores and the pack's loads.)
 // heads[perspective] = {nHi | nLds << 6 | nCold << 15, 2 * position + (0 = side-to-move half, 1 = other half), sort key, -}
 constexpr uint32_t kFtxListStride = 576, kFtxListLds = 0, kFtxListHi = 288, kFtxListCold = 320;
 // sort key of a perspective: king bucket * 80 + min(global quartets >> coldShift, 15) * 5 + min(LDS quartets >> 2, 4) - the quartets
@@ -115,7 +116,7 @@ struct FtxParams {
     uint32_t nPositions;
     FtTables t;              // lut, deltaTab (pseudo-attack sets), ftBias
     const uint8_t* rowS;     // the sliced row table
-    uint32_t* lists;         // [2 n][kFtxListStride]
+    uint16_t* lists;         // [2 n][kFtxListStride]
     uint32_t* heads;         // [2 n][4]
     uint32_t* ranks;         // [2 n] rank inside the key's bin
     uint32_t* hist;          // [kFtxBins] counts per key; zero on entry of the rank kernel, zeroed again by the plan kernel
@@ -141,7 +142,7 @@ struct FtxParams {
     uint32_t* mlpHist;       // [kHistOut + 8] out: the counts at [kHistOut + bucket]
 };
 
-inline size_t ftxListBytes(size_t n) { return 2 * n * size_t(kFtxListStride) * 4; }
+inline size_t ftxListBytes(size_t n) { return 2 * n * size_t(kFtxListStride) * 2; }
 inline size_t ftxGroups(size_t n) { return (2 * n + 128) / 8; }
 inline size_t ftxStageBytes(size_t n) { return ftxGroups(n) * kFtxMaxStages * 1024; }
 

@@ -21,8 +21,8 @@
 //
 // Pipeline (all on one stream; on the three lanes of the pipelined entry point the preparation of two batches runs beside a gather):
 //   spx_ftx_extract_kernel  one wave per POSITION: board decode, attack sets and the feature candidates once, the row lists of both
-//                           perspectives (nnue_state.cpp:309-354, 440-449) to HBM - LDS section (piece-square rows, hot rows),
-//                           high-byte planes, cold rows -, a head and a sort key (king bucket, global quartets, LDS quartets)
+//                           perspectives (nnue_state.cpp:309-354, 440-449) to HBM as 16-bit row indices - LDS section (piece-square
+//                           rows, hot rows), high-byte planes, cold rows -, a head and a sort key (king bucket, global quartets, LDS quartets)
 //   spx_ftx_rank_kernel     counting sort, part 1: rank of every perspective inside its key's bin (and, round 6, of every position
 //                           inside its OUTPUT bucket: a one-pass batch gets the MLP's order - posOrder - from this sort as well)
 //   spx_ftx_plan_kernel     bin starts (each bucket padded to whole groups of 8), and the PLAN: the groups cut into 32
@@ -127,8 +127,8 @@ __global__ void spx_ftx_build_himask_kernel(const uint8_t* rowS, uint32_t* hiMas
 // Extraction: one wave per position, lane = square. Everything that does not depend on the perspective is done once (VERDICT
 // r3 item 5): the record decode, the attack sets, and the ENUMERATION of the feature candidates - every (attacker, victim)
 // pair and every pawn pair becomes one item of a flat list in LDS (a wave scan of the lanes' counts places them; each lane then
-// writes its own, as many rounds as the busiest square has targets). Each perspective then turns the items into rows 64 at a
-// time - typically one round per kind instead of one per target of the busiest square - and writes them straight to its list.
+// writes its own, as many rounds as the busiest square has targets). One pass turns the items into the rows of BOTH perspectives
+// 64 at a time - typically one round - and writes them straight to the two lists: an item is read and its pieces shuffled once.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t kItemCap = 256;  // per kind: <= 30 attackers x 8 targets; malformed records are cut off here
 // threat items: attacker square | victim square << 6; pawn items: from | to << 6 | (1 = same colour (from < to), 0 = different
@@ -202,15 +202,19 @@ __global__ __launch_bounds__(64 * kExtractWaves, 2) void spx_ftx_extract_kernel(
             }
         }
         __builtin_amdgcn_wave_barrier();
-#pragma unroll 1
+        // both perspectives in one pass (round 7): c = 0 (black) and c = 1 (white) side by side, every item read and its pieces
+        // shuffled once. Everything indexed by c is wave uniform.
+        int x[2];
+        uint32_t bucket[2], nPsq[2], nHi[2], nThr[2] = {0, 0}, nHot[2] = {0, 0}, nCold[2] = {0, 0};
+        uint16_t* out[2];
+        const uint32_t psqSlot = prefixCount(b.occ);
+#pragma unroll
         for (int c = 0; c < 2; ++c) {
             const uint64_t ownKing = __ballot(piece == (10 | c));
             const int kingSq = ownKing ? ctz64(ownKing) : 0;  // a record without that king is malformed: stay in bounds
-            const int x = perspXor(c, kingSq);
-            const int flipColour = (c == 0) ? 1 : 0;
-            const uint32_t bucket = uint32_t(kingBucket(c == 0 ? (kingSq ^ 56) : kingSq));
-            const uint32_t q = 2 * pos + uint32_t(c);
-            uint32_t* out = p.lists + size_t(q) * kFtxListStride;
+            x[c] = perspXor(c, kingSq);
+            bucket[c] = uint32_t(kingBucket(c == 0 ? (kingSq ^ 56) : kingSq));
+            out[c] = p.lists + size_t(2 * pos + uint32_t(c)) * kFtxListStride;
             // piece-square rows (resetPsqAccumulator, nnue_state.cpp:440-449): every one from the bucket's LDS slab; a row
             // with weights outside i8 also has a high-byte plane to fetch
             uint32_t row = 0;
@@ -220,69 +224,75 @@ __global__ __launch_bounds__(64 * kExtractWaves, 2) void spx_ftx_extract_kernel(
                 wide = !((sLut[kLutCompactBase + (row >> 5)] >> (row & 31)) & 1u);
             }
             const uint64_t wideMask = __ballot(wide);
-            const uint32_t slot = prefixCount(b.occ), wideSlot = prefixCount(wideMask);
-            if (occupied && slot < kPsqCap) {
-                out[kFtxListLds + slot] = (row - bucket * kFtxSlabRows) * 128u;  // (an LDS offset: the slab heads the gather's LDS)
-                if (wide && wideSlot < kPsqCap) out[kFtxListHi + wideSlot] = (kFtxPsqHiBase + row) * 128u;
+            const uint32_t wideSlot = prefixCount(wideMask);
+            if (occupied && psqSlot < kPsqCap) {
+                out[c][kFtxListLds + psqSlot] = uint16_t(row - bucket[c] * kFtxSlabRows);  // (slab row: the slab heads the gather's LDS)
+                if (wide && wideSlot < kPsqCap) out[c][kFtxListHi + wideSlot] = uint16_t(row);
             }
-            const uint32_t nPsq = min(uint32_t(popc64(b.occ)), uint32_t(kPsqCap));
-            const uint32_t nHi = min(uint32_t(popc64(wideMask)), uint32_t(kPsqCap));
-            // threat / pawn-pair rows: a row of the context's hot set (LDS resident in the gather) joins the piece-square rows in the
-            // LDS section as an LDS offset, any other goes to the cold section as a slice offset; 256 rows in all, in the order of
-            // enumeration, like the reference's StaticVector<u16, 256> (nnue_state.cpp:315)
-            uint32_t nThr = 0, nHot = 0, nCold = 0;
-            auto emit = [&](int32_t r) {
-                const uint64_t valid = __ballot(r >= 0);
-                const bool taken = r >= 0 && nThr + prefixCount(valid) < kThreatCap;
-                uint32_t slot = 0xFFFFu;
-                if (taken) {  // the hot set's hash: bucket (row * multiplier) >> 24 mod 256, four entries row | slot << 16
-                    const u32x4 e = *reinterpret_cast<const u32x4*>(sHot + 4 * ((__umul24(uint32_t(r), p.hotHashMul) >> 16) & (kFtxHotHashWords / 4 - 1)));
+            nPsq[c] = min(uint32_t(popc64(b.occ)), uint32_t(kPsqCap));
+            nHi[c] = min(uint32_t(popc64(wideMask)), uint32_t(kPsqCap));
+        }
+        // threat / pawn-pair rows: a row of the context's hot set (LDS resident in the gather) joins the piece-square rows in the
+        // LDS section as 705 + its slot, any other goes to the cold section as its row index; 256 rows in all, in the order of
+        // enumeration, like the reference's StaticVector<u16, 256> (nnue_state.cpp:315)
+        auto emit = [&](int c, int32_t r) {
+            const uint64_t valid = __ballot(r >= 0);
+            const bool taken = r >= 0 && nThr[c] + prefixCount(valid) < kThreatCap;
+            uint32_t slot = 0xFFFFu;
+            if (taken) {  // the hot set's hash: bucket (row * multiplier) >> 24 mod 256, four entries row | slot << 16
+                const u32x4 e = *reinterpret_cast<const u32x4*>(sHot + 4 * ((__umul24(uint32_t(r), p.hotHashMul) >> 16) & (kFtxHotHashWords / 4 - 1)));
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if ((e[i] & 0xFFFFu) == uint32_t(r)) slot = e[i] >> 16;
-                    }
+                for (int i = 0; i < 4; ++i) {
+                    if ((e[i] & 0xFFFFu) == uint32_t(r)) slot = e[i] >> 16;
                 }
-                const bool hot = taken && slot != 0xFFFFu, cold = taken && !hot;
-                const uint64_t hotMask = __ballot(hot), coldMask = __ballot(cold);
-                // ONE store for both kinds (beside a gather every vector-memory instruction of this kernel queues behind the gather's
-                // row loads: without the list stores the pass took 223 instead of 272 us there, profiles/r05_gather_anatomy.txt)
-                if (taken) {
-                    uint32_t* at = out + (hot ? kFtxListLds + nPsq + nHot + prefixCount(hotMask) : kFtxListCold + nCold + prefixCount(coldMask));
-                    const uint32_t v = hot ? kFtxSlabBytes + slot * 128u : uint32_t(r) * 128u;
-                    if (SPX_FTX_NT & 8) __builtin_nontemporal_store(v, at);
-                    else *at = v;
-                }
-                nHot += uint32_t(popc64(hotMask));
-                nCold += uint32_t(popc64(coldMask));
-                nThr = min(nThr + uint32_t(popc64(valid)), uint32_t(kThreatCap));
-            };
-            // threat rows (addThreatFeatures, nnue_state.cpp:309-328: the reference drops the pairs whose index is negative), then
-            // the pawn pairs (:330-351) - ONE walk over the items of both kinds, 64 at a time (a position has ~55: one round)
-            const uint32_t nItems = nThreatItems + nPawnItems;
-            for (uint32_t base = 0; base < nItems; base += 64) {
-                const bool active = base + lane < nItems;
-                const uint32_t item = active ? items[base + lane] : 0u;
-                const int from = item & 63u, to = (item >> 6) & 63u;
-                const int pieceFrom = __shfl(piece, from, 64), pieceTo = __shfl(piece, to, 64);
+            }
+            const bool hot = taken && slot != 0xFFFFu, cold = taken && !hot;
+            const uint64_t hotMask = __ballot(hot), coldMask = __ballot(cold);
+            // ONE store for both kinds (beside a gather every vector-memory instruction of this kernel queues behind the gather's
+            // row loads: without the list stores the pass took 223 instead of 272 us there, profiles/r05_gather_anatomy.txt)
+            if (taken) {
+                uint16_t* at = out[c] + (hot ? kFtxListLds + nPsq[c] + nHot[c] + prefixCount(hotMask) : kFtxListCold + nCold[c] + prefixCount(coldMask));
+                const uint16_t v = uint16_t(hot ? kFtxSlabRows + 1 + slot : uint32_t(r));
+                if (SPX_FTX_NT & 8) __builtin_nontemporal_store(v, at);
+                else *at = v;
+            }
+            nHot[c] += uint32_t(popc64(hotMask));
+            nCold[c] += uint32_t(popc64(coldMask));
+            nThr[c] = min(nThr[c] + uint32_t(popc64(valid)), uint32_t(kThreatCap));
+        };
+        // threat rows (addThreatFeatures, nnue_state.cpp:309-328: the reference drops the pairs whose index is negative), then
+        // the pawn pairs (:330-351) - ONE walk over the items of both kinds, 64 at a time (a position has ~55: one round)
+        const uint32_t nItems = nThreatItems + nPawnItems;
+        for (uint32_t base = 0; base < nItems; base += 64) {
+            const bool active = base + lane < nItems;
+            const uint32_t item = active ? items[base + lane] : 0u;
+            const int from = item & 63u, to = (item >> 6) & 63u;
+            const int pieceFrom = __shfl(piece, from, 64), pieceTo = __shfl(piece, to, 64);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int flipColour = c == 0 ? 1 : 0;
                 int32_t r = -1;
                 if (active && !(item & 0x8000u)) {
-                    const int pieceRel = pieceFrom ^ flipColour, victimRel = pieceTo ^ flipColour, sqRel = from ^ x;
+                    const int pieceRel = pieceFrom ^ flipColour, victimRel = pieceTo ^ flipColour, sqRel = from ^ x[c];
                     const uint64_t pseudoRel = sPseudo[(pieceRel >= 2 ? (pieceRel >> 1) + 1 : pieceRel) * 64 + sqRel];
-                    r = threatRow(sLut, pieceRel, sqRel, pseudoRel, victimRel, to ^ x);
+                    r = threatRow(sLut, pieceRel, sqRel, pseudoRel, victimRel, to ^ x[c]);
                 } else if (active) {
                     const bool sameColour = (item >> 12) & 1u, own = (pieceFrom & 1) == c;
-                    if (sameColour || own) r = int32_t(ppRow(ppId(from ^ x, !own), ppId(to ^ x, sameColour ? !own : true)));
+                    if (sameColour || own) r = int32_t(ppRow(ppId(from ^ x[c], !own), ppId(to ^ x[c], sameColour ? !own : true)));
                 }
-                emit(r);
+                emit(c, r);
             }
-            if (lane == 0) {
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
                 u32x4 head;
-                head[0] = nHi | ((nPsq + nHot) << 6) | (nCold << 15);
+                head[0] = nHi[c] | ((nPsq[c] + nHot[c]) << 6) | (nCold[c] << 15);
                 head[1] = 2 * pos + ((c == b.stm) ? 0u : 1u);  // stm half first (nnue_state.cpp:396-438)
-                const uint32_t globalQ = (nHi + 3) / 4 + (nCold + 3) / 4, ldsQ = (nPsq + nHot + 3) / 4;
-                head[2] = ftxSortKey(bucket, globalQ, ldsQ, p.coldShift);
+                const uint32_t globalQ = (nHi[c] + 3) / 4 + (nCold[c] + 3) / 4, ldsQ = (nPsq[c] + nHot[c] + 3) / 4;
+                head[2] = ftxSortKey(bucket[c], globalQ, ldsQ, p.coldShift);
                 head[3] = min((uint32_t(popc64(b.occ)) - 2u) / 4u, 7u);  // output bucket (MaterialCount<8>, output.h:44-55): FtxParams::posOrder
-                *reinterpret_cast<u32x4*>(p.heads + 4 * size_t(q)) = head;
+                *reinterpret_cast<u32x4*>(p.heads + 4 * size_t(2 * pos + uint32_t(c))) = head;
             }
         }
         __builtin_amdgcn_wave_barrier();  // (the next position's items overwrite these)
@@ -512,7 +522,7 @@ __global__ void spx_ftx_scatter_kernel(FtxParams p) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= 2 * p.nPositions) return;
     const u32x4 head = *reinterpret_cast<const u32x4*>(p.heads + 4 * size_t(q));
-    reinterpret_cast<u32x4*>(p.sorted)[p.binStart[head[2]] + p.ranks[q]] = u32x4{head[0], head[1], q * (kFtxListStride * 4u), q};
+    reinterpret_cast<u32x4*>(p.sorted)[p.binStart[head[2]] + p.ranks[q]] = u32x4{head[0], head[1], q * (kFtxListStride * 2u), q};
     if (p.posOrder && !(q & 1u)) p.posOrder[p.binStart[kFtxBins + 17 + (head[3] & 7u)] + (head[3] >> 3)] = q >> 1;
 }
 
@@ -571,11 +581,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void spx_ftx_pack_kernel(FtxPa
     // ---- the high-byte section: stages of 8 steps, 32-bit entries (slice offset | hiMask << 24): the gather compacts them per slice ----
     for (uint32_t q = 0; q < H; ++q) {
         const uint32_t first = 4 * (8 * q + ks), left = cHi > first ? cHi - first : 0u;
-        u32x4 v = {0, 0, 0, 0};
-        if (left) v = *reinterpret_cast<const u32x4*>(lists + head[2] + 4 * (kFtxListHi + first));
+        u32x2 rows = {0, 0};  // four 16-bit piece-square rows
+        if (left) rows = *reinterpret_cast<const u32x2*>(lists + head[2] + 2 * (kFtxListHi + first));
+        u32x4 v;
 #pragma unroll
         for (uint32_t i = 0; i < 4; ++i) {  // in which slices the plane is not all zero (bits 24-31; the entry itself < 2^24)
-            if (left > i) v[i] |= uint32_t(p.hiMask[(v[i] >> 7) - kFtxPsqHiBase]) << 24;
+            const uint32_t row = (rows[i >> 1] >> (16 * (i & 1u))) & 0xFFFFu;
+            v[i] = (kFtxPsqHiBase + row) * 128u;
+            if (left > i) v[i] |= uint32_t(p.hiMask[row]) << 24;
         }
         uint32_t* st = &sStage[wave][fillAt];
         st[0] = left > 0 ? v[0] : kFtxZeroRow * 128u;
@@ -598,29 +611,29 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void spx_ftx_pack_kernel(FtxPa
         const uint32_t shift = min((isCold ? coldQ : ldsQ) - 16 * s, 16u) & 1u, k = ks + 8 * c;
         const uint32_t count = isCold ? cCold : cLds, first = 4 * (16 * s + k - shift);
         left = (k >= shift && count > first) ? count - first : 0u;
-        at = head[2] + 4 * ((isCold ? kFtxListCold : kFtxListLds) + first);
+        at = head[2] + 2 * ((isCold ? kFtxListCold : kFtxListLds) + first);
     };
     uint32_t at[2] = {0, 0}, left[2] = {0, 0};
-    u32x4 next[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    u32x2 next[2] = {{0, 0}, {0, 0}};  // four 16-bit entries each
     if (Q > H) {
 #pragma unroll
         for (uint32_t c = 0; c < 2; ++c) {
             place(H, c, at[c], left[c]);
-            if (left[c]) next[c] = *reinterpret_cast<const u32x4*>(lists + at[c]);
+            if (left[c]) next[c] = *reinterpret_cast<const u32x2*>(lists + at[c]);
         }
     }
     uint16_t* const sHalf = reinterpret_cast<uint16_t*>(sStage[wave]);
     const uint32_t u = g & 1u, pr = g >> 1;
     for (uint32_t q = H; q < Q; ++q) {
-        const u32x4 v[2] = {next[0], next[1]};
+        const u32x2 v[2] = {next[0], next[1]};
         const uint32_t leftNow[2] = {left[0], left[1]};
         const uint32_t zero = q >= H + L ? kFtxColdZeroRow : kFtxSlabRows;  // (the table's zero row behind the threat rows / the slab's)
         if (q + 1 < Q) {
 #pragma unroll
             for (uint32_t c = 0; c < 2; ++c) {
                 place(q + 1, c, at[c], left[c]);
-                next[c] = u32x4{0, 0, 0, 0};
-                if (left[c]) next[c] = *reinterpret_cast<const u32x4*>(lists + at[c]);
+                next[c] = u32x2{0, 0};
+                if (left[c]) next[c] = *reinterpret_cast<const u32x2*>(lists + at[c]);
             }
         }
 #pragma unroll
@@ -628,7 +641,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void spx_ftx_pack_kernel(FtxPa
             const uint32_t k = ks + 8 * c;  // halfword ((k >> 1) * 8 + 2 kb + u) * 8 + (k & 1) * 4 + pr: row kb of step k, perspective 2 pr + u
             uint16_t* st = sHalf + ((k >> 1) * 8 + u) * 8 + (k & 1u) * 4 + pr;
 #pragma unroll
-            for (uint32_t kb = 0; kb < 4; ++kb) st[16 * kb] = uint16_t(leftNow[c] > kb ? v[c][kb] >> 7 : zero);
+            for (uint32_t kb = 0; kb < 4; ++kb) st[16 * kb] = uint16_t(leftNow[c] > kb ? v[c][kb >> 1] >> (16 * (kb & 1u)) : zero);
         }
         __builtin_amdgcn_wave_barrier();
         const u32x4 line = *reinterpret_cast<const u32x4*>(&sStage[wave][4 * lane]);
@@ -944,8 +957,8 @@ __global__ void spx_ftx_hist_kernel(FtxParams p, uint32_t* counts, uint32_t* sta
     for (uint32_t q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; q < nPersp; q += (gridDim.x * blockDim.x) >> 6) {
         const uint32_t head = p.heads[4 * size_t(q)];
         const uint32_t nCold = head >> 15;
-        const uint32_t* list = p.lists + size_t(q) * kFtxListStride + kFtxListCold;
-        for (uint32_t i = lane; i < nCold; i += 64) atomicAdd(&counts[list[i] >> 7], 1u);
+        const uint16_t* list = p.lists + size_t(q) * kFtxListStride + kFtxListCold;
+        for (uint32_t i = lane; i < nCold; i += 64) atomicAdd(&counts[list[i]], 1u);
         if (lane == 0) hi += head & 0x3Fu;
     }
     if (hi) atomicAdd(&stats[0], hi);
