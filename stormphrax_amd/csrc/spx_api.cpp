@@ -38,6 +38,15 @@ void buildDeltaTables(uint64_t* tab);  // spx_luts.cpp
 
 using namespace spx;
 
+#define SPX_HIP(call)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            setError(std::string(#call) + ": " + hipGetErrorString(e_));                           \
+            return SPX_ERR_HIP;                                                                    \
+        }                                                                                          \
+    } while (0)
+
 struct spx_net {
     std::vector<unsigned char> blob;  // full file image, logical layout
     std::string name;
@@ -64,6 +73,55 @@ struct FtxScratch {
     }
 };
 
+// what one call sequence writes between its launches: the context's own set, and one per lane (spx_ctx::EvalLane), so that calls
+// on different streams never share a buffer
+struct ScratchSet {
+    uint8_t* dFtOut = nullptr;
+    uint8_t* dKingKeys = nullptr;  // counting-sort scratch
+    uint8_t* dOutKeys = nullptr;
+    uint8_t* dStaged = nullptr;       // [max_batch][32] records of the slots being evaluated
+    uint32_t* dHist = nullptr;        // 3 sort-histogram buffers of kHistWords + 64 words of counters
+    uint32_t* dPerspOrder = nullptr;  // perspective ids grouped by king bucket
+    uint32_t* dPosOrder = nullptr;    // position ids grouped by output bucket
+    uint32_t* dRefreshList = nullptr; // update kernel: perspectives deferred to the rebuild pass (its own buffer: the king sort
+                                      // of a full refresh on another stream must not overwrite a list that is being consumed)
+    uint32_t* histUsed = nullptr;  // the buffer the latest sort wrote (what the MLP kernel reads)
+    int histCur = 0;               // dHist: buffers [0],[1] alternate between large sorts (each sort clears the other one
+                                   // for its successor), [2] belongs to the single-launch small sort; behind them words
+                                   // 0,1: alternating counters of the update kernel's deferred-refresh list
+    int refreshCur = 0;            // which of the two counters the next update uses (its refresh pass clears the other)
+    FtxScratch ftx;                // the column-sliced pipeline's (allocated on first use)
+
+    // (the dHist memset runs on the null stream: the caller synchronises the device before another stream uses the set)
+    int allocate(size_t maxBatch) {
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&dFtOut), maxBatch * size_t(kL1)));
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&dKingKeys), maxBatch * 2));
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&dOutKeys), maxBatch));
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&dStaged), maxBatch * 32));
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&dHist), (3 * kHistWords + 64) * sizeof(uint32_t)));
+        SPX_HIP(hipMemset(dHist, 0, (3 * kHistWords + 64) * sizeof(uint32_t)));
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&dPerspOrder), maxBatch * 2 * sizeof(uint32_t)));
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&dPosOrder), maxBatch * sizeof(uint32_t)));
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&dRefreshList), maxBatch * 2 * sizeof(uint32_t)));
+        return SPX_OK;
+    }
+    void release() {
+        void* ptrs[] = {dFtOut, dKingKeys, dOutKeys, dStaged, dHist, dPerspOrder, dPosOrder, dRefreshList};
+        for (void* q : ptrs) {
+            if (q) (void)hipFree(q);
+        }
+        ftx.release();
+        *this = ScratchSet{};
+    }
+};
+
+// a lane's call: its FT kernel waits for `wait` and signals `record` (the lanes' big kernels are chained); `pace`: the events an
+// unprofiled pipelined call records (see spx_ctx::paceEnabled)
+struct CallGates {
+    hipEvent_t wait = nullptr, record = nullptr;
+    hipEvent_t* pace = nullptr;
+};
+
 struct spx_ctx {
     int device = 0;
     size_t maxBatch = 0;       // scratch capacity: positions one launch sequence can hold intermediates for
@@ -74,7 +132,6 @@ struct spx_ctx {
     int16_t* dPsqW = nullptr;
     uint8_t* dThrW = nullptr;
     uint8_t* dRowS = nullptr;   // the column-sliced row table of spx_ftx.hip (built on first use)
-    FtxScratch ftx;             // its scratch (the lanes hold their own)
     // the gather's hot set: the threat / pawn-pair rows it keeps in LDS beside the piece-square slab (spx_ftx.h). Chosen from DATA - a
     // histogram over the first batch that takes the pipeline (calibrateHotRows) or over the batch handed to spx_ctx_calibrate -;
     // results never depend on it. Per context: the ranks of a multi-GPU job calibrate independently.
@@ -95,7 +152,7 @@ struct spx_ctx {
     int ftxFailLaunch = -1;  // (option ftx_fail_launch: the k-th sliced pass from now reports a launch failure; -1: never)
     bool ftxMinForced = false;    // (ftx_min given: the same threshold for stream-ordered and pipelined calls)
     bool ftxUnavailable = false;  // its table or scratch did not fit the device memory
-    // (spx_eval_full_device_async: each lane has its own scratch set - swapLane -, so one lane's preparation runs beside the
+    // (spx_eval_full_device_async: each lane has its own scratch set, so one lane's preparation runs beside the
     // other lane's gather. A ring of extra streams that prepared up to three batches ahead cost 12 %: 1.60 against 1.81e8
     // evals/s - more streams than hardware queues serialise; profiles/r04_sliced_pipeline_overlap_attempts.txt)
     int16_t* dFtBias = nullptr;
@@ -109,48 +166,48 @@ struct spx_ctx {
     // scratch
     void* dPositions = nullptr;  // staging for the host-buffer entry point
     int32_t* dOut = nullptr;
-    uint8_t* dFtOut = nullptr;
-    uint8_t* dKingKeys = nullptr;  // counting-sort scratch
-    uint8_t* dOutKeys = nullptr;
-    uint32_t* dHist = nullptr;     // 3 sort-histogram buffers of kHistWords + 64 words of counters
-    uint32_t* dPerspOrder = nullptr;  // perspective ids grouped by king bucket
-    uint32_t* dPosOrder = nullptr;    // position ids grouped by output bucket
-    uint32_t* dRefreshList = nullptr; // update kernel: perspectives deferred to the rebuild pass (its own buffer: the king sort
-                                      // of a full refresh on another stream must not overwrite a list that is being consumed)
+    ScratchSet own;
+    ScratchSet* active = &own;  // the set the entry points use: a lane's while a call runs on it (enterLane)
+    CallGates gates;            // set while a call runs on a lane
     // accumulator arena (incremental path): nSlots x (4 KiB accumulators + 32 B record)
     uint8_t* dArena = nullptr;
     uint8_t* dSlotRecords = nullptr;
     size_t nSlots = 0;
     uint32_t *dSlotsA = nullptr, *dSlotsB = nullptr;  // staging for the host-buffer entry points [max_batch]
-    uint8_t* dStaged = nullptr;                        // [max_batch][32] records of the slots being evaluated
     uint8_t* dDeltas = nullptr;                        // [max_batch] spx_move_delta staging (allocated on first use)
-    int histCur = 0;               // dHist: buffers [0],[1] alternate between large sorts (each sort clears the other one
-                                   // for its successor), [2] belongs to the single-launch small sort; behind them words
-                                   // 0,1: alternating counters of the update kernel's deferred-refresh list
-    int refreshCur = 0;            // which of the two counters the next update uses (its refresh pass clears the other)
-    uint32_t* histUsed = nullptr;  // the buffer the latest sort wrote (what the MLP kernel reads)
     // spx_eval_full_device_async: two scratch sets ("lanes") with their own streams alternate, so that the sorts and
     // the MLP of one batch run beside the feature-transformer kernel of the next; the FT kernels themselves are
     // chained by events (they never overlap each other - two of them thrash the caches)
     struct EvalLane {
-        uint8_t *dFtOut = nullptr, *dKingKeys = nullptr, *dOutKeys = nullptr, *dStaged = nullptr;
-        uint32_t *dHist = nullptr, *dPerspOrder = nullptr, *dPosOrder = nullptr, *dRefreshList = nullptr, *histUsed = nullptr;
-        int histCur = 0, refreshCur = 0;
+        ScratchSet set;
         hipStream_t stream = nullptr;
         hipEvent_t ftDone = nullptr, done = nullptr;
-        hipEvent_t pace[kProfEventsPerCall] = {};  // see spx_ctx::paceEvents
+        hipEvent_t pace[kProfEventsPerCall] = {};  // see spx_ctx::paceEnabled
         bool ftRecorded = false;
         // staging of the chunked host-buffer call (allocated on its first use): device in/out + page-locked mirrors
         void *dIn = nullptr, *hIn = nullptr;
         int32_t *dOutStage = nullptr, *hOut = nullptr;
-        FtxScratch ftx;
+        void release() {
+            if (stream) (void)hipStreamSynchronize(stream);
+            set.release();
+            if (dIn) (void)hipFree(dIn);
+            if (dOutStage) (void)hipFree(dOutStage);
+            if (hIn) (void)hipHostFree(hIn);
+            if (hOut) (void)hipHostFree(hOut);
+            if (ftDone) (void)hipEventDestroy(ftDone);
+            if (done) (void)hipEventDestroy(done);
+            for (hipEvent_t e : pace) {
+                if (e) (void)hipEventDestroy(e);
+            }
+            if (stream) (void)hipStreamDestroy(stream);
+            *this = EvalLane{};
+        }
     } lanes[3];  // (the third one serves spx_eval_full_device_async alone: option eval_lanes)
     unsigned evalLanes = 3;
     bool lanesReady = false;
     bool lanesUnavailable = false;   // the lanes did not fit into the device memory: async calls run stream-ordered
     hipEvent_t fallbackDone = nullptr;
     unsigned laneNext = 0;
-    hipEvent_t ftGateWait = nullptr, ftGateRecord = nullptr;  // set around a lane's call: FT waits / signals
     size_t tinyBatchMax = 0;       // spx_eval_full*: batches up to this size skip the sorts (one MLP tile per position)
     void* hTinyIo = nullptr;       // page-locked, device-mapped staging of the tiny-batch host call: records, then scores
     size_t mlpShareMax = 0;        // spx_mlp_kernel: positions up to which four waves share one 16-position tile
@@ -172,13 +229,9 @@ struct spx_ctx {
     // Pipelined calls record an event at the five points of a call where spx_profile_* would (round 6): measured on the sustained
     // loop of tools/probes/sustained_rate.py, the three lanes settle into 2.12e8 evals/s with those records in their streams and into
     // 1.89e8 without - the records hold a lane's next preparation back until what the lane ran before has fully drained. Nobody reads
-    // them (option pace_events = 0: none, unless a profile is open; pace_mask / pace_head_extra: which).
-    hipEvent_t* paceEvents = nullptr;
+    // them (option pace_events = 0: none, unless a profile is open). Of the five, three records in front of the extraction are
+    // the measured best: [0] twice at the head of the call, [1] after the sort (2.18e8; the A/B: docs/experiments.md)
     bool paceEnabled = true;
-    // which of the five, and extra records at the head of the call (A/B on the sustained loop, x 1e8 evals/s: none 1.89 - all five 2.14 -
-    // only the two at the head 2.16 - those + one more 2.18 - + two / four more 2.17 / 2.15; the one behind the gather alone 2.10, with
-    // the head's 2.11; the one before the gather alone: nothing): three records in front of the extraction
-    uint32_t paceMask = 3, paceHeadExtra = 1;
     bool ftxFoldSort = true;       // option ftx_fold_sort: one-pass batches of the pipeline sort the MLP's order themselves
     uint32_t computeUnits = 0;
     uint32_t ftGridCap = 0;
@@ -213,15 +266,6 @@ int64_t ctxSelfplayOption(const spx_ctx* ctx, int which) {
 }  // namespace spx
 
 namespace {
-
-#define SPX_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            setError(std::string(#call) + ": " + hipGetErrorString(e_));                           \
-            return SPX_ERR_HIP;                                                                    \
-        }                                                                                          \
-    } while (0)
 
 // Header checks in the order of the reference's validate() (nnue.cpp:85-185); messages name the same conditions.
 int validateHeader(const unsigned char* h, std::string& name) {
@@ -586,14 +630,6 @@ int spx_ctx_set_option(spx_ctx* ctx, const char* name, int64_t value) {
         ctx->ftxFailLaunch = int(value);
         return SPX_OK;
     }
-    if (key == "pace_head_extra") {
-        ctx->paceHeadExtra = uint32_t(value);
-        return SPX_OK;
-    }
-    if (key == "pace_mask") {
-        ctx->paceMask = uint32_t(value);
-        return SPX_OK;
-    }
     if (key == "pace_events") {  // pipelined calls: an event record at the five points of a call where a profile would put one (1) or none (0)
         ctx->paceEnabled = value != 0;
         return SPX_OK;
@@ -781,17 +817,9 @@ int spx_ctx_create_opts(const spx_net* net, int device, size_t max_batch, uint32
     }
     SPX_HIP(hipMalloc(&ctx->dPositions, max_batch * sizeof(spx_packed_pos)));
     SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dOut), max_batch * sizeof(int32_t)));
-    SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dFtOut), max_batch * size_t(kL1)));
-    SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dKingKeys), max_batch * 2));
-    SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dOutKeys), max_batch));
-    SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dHist), (3 * kHistWords + 64) * sizeof(uint32_t)));
-    SPX_HIP(hipMemset(ctx->dHist, 0, (3 * kHistWords + 64) * sizeof(uint32_t)));
-    SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dPerspOrder), max_batch * 2 * sizeof(uint32_t)));
-    SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dPosOrder), max_batch * sizeof(uint32_t)));
-    SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dRefreshList), max_batch * 2 * sizeof(uint32_t)));
+    if ((rc = ctx->own.allocate(max_batch)) != SPX_OK) return rc;
     SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dSlotsA), max_batch * sizeof(uint32_t)));
     SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dSlotsB), max_batch * sizeof(uint32_t)));
-    SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dStaged), max_batch * 32));
     ctx->ftxEnabled = !(flags & (SPX_CTX_ONE_KERNEL_FT | SPX_CTX_WIDE_PSQ_ROWS)) || (flags & SPX_CTX_SLICED_FT);
     // A/B on MI355X (tools/gpu_small_ab.sh, us per incremental ply unsplit/unshared -> split+shared): 1 024 records
     // 52.5 -> 34.0, 4 096: 60.3 -> 53.4, 8 192: 87.4 -> 81.8; split alone 32 768: 263 -> 247, 65 536: 471 -> 455,
@@ -832,13 +860,12 @@ void spx_ctx_destroy(spx_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     void* ptrs[] = {ctx->dPsqW, ctx->dThrW, ctx->dFtBias, ctx->dL1W, ctx->dL1B, ctx->dL2W,  ctx->dL2B,
-                    ctx->dL3W,  ctx->dL3B, ctx->dLut,    ctx->dDeltaTab, ctx->dOutlierTab, ctx->dPositions, ctx->dOut, ctx->dFtOut,
-                    ctx->dKingKeys, ctx->dOutKeys, ctx->dHist, ctx->dPerspOrder, ctx->dPosOrder, ctx->dRefreshList,
-                    ctx->dArena, ctx->dSlotRecords, ctx->dSlotsA, ctx->dSlotsB, ctx->dStaged, ctx->dDeltas};
+                    ctx->dL3W,  ctx->dL3B, ctx->dLut,    ctx->dDeltaTab, ctx->dOutlierTab, ctx->dPositions, ctx->dOut,
+                    ctx->dArena, ctx->dSlotRecords, ctx->dSlotsA, ctx->dSlotsB, ctx->dDeltas};
     for (void* p : ptrs) {
         if (p) (void)hipFree(p);
     }
-    ctx->ftx.release();
+    ctx->own.release();
     for (void* q : {static_cast<void*>(ctx->dRowS), static_cast<void*>(ctx->dHotHash), static_cast<void*>(ctx->dHotS),
                     static_cast<void*>(ctx->dHotIds), static_cast<void*>(ctx->dHotCounts), static_cast<void*>(ctx->dHiMask)}) {
         if (q) (void)hipFree(q);
@@ -846,57 +873,41 @@ void spx_ctx_destroy(spx_ctx* ctx) {
     for (hipEvent_t e : ctx->profEvents) (void)hipEventDestroy(e);
     if (ctx->hTinyIo) (void)hipHostFree(ctx->hTinyIo);
     if (ctx->fallbackDone) (void)hipEventDestroy(ctx->fallbackDone);
-    for (auto& lane : ctx->lanes) {
-        if (lane.stream) (void)hipStreamSynchronize(lane.stream);
-        void* lanePtrs[] = {lane.dFtOut, lane.dKingKeys, lane.dOutKeys, lane.dStaged, lane.dHist, lane.dPerspOrder,
-                            lane.dPosOrder, lane.dRefreshList, lane.dIn, lane.dOutStage};
-        if (lane.hIn) (void)hipHostFree(lane.hIn);
-        if (lane.hOut) (void)hipHostFree(lane.hOut);
-        for (void* q : lanePtrs) {
-            if (q) (void)hipFree(q);
-        }
-        lane.ftx.release();
-        if (lane.ftDone) (void)hipEventDestroy(lane.ftDone);
-        if (lane.done) (void)hipEventDestroy(lane.done);
-        for (hipEvent_t e : lane.pace) {
-            if (e) (void)hipEventDestroy(e);
-        }
-        if (lane.stream) (void)hipStreamDestroy(lane.stream);
-    }
+    for (auto& lane : ctx->lanes) lane.release();
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
 
-// sort (both keys) on `d_records`, then the MLP over ctx->dFtOut[0..n) -> d_out
-static int runSortAndMlp(spx_ctx* ctx, const void* d_records, size_t n, void* d_out, hipStream_t s, bool mlp,
-                         const uint32_t* d_count = nullptr, bool outOnly = false) {
+// sort (both keys) on `d_records`, then the MLP over x.dFtOut[0..n) -> d_out
+static int runSortAndMlp(const spx_ctx* ctx, ScratchSet& x, const void* d_records, size_t n, void* d_out, hipStream_t s,
+                         bool mlp, const uint32_t* d_count = nullptr, bool outOnly = false) {
     if (!mlp) {
         SortParams sp{};
         sp.positions = static_cast<const uint64_t*>(d_records);
         sp.nPositions = uint32_t(n);
         sp.nPositionsPtr = d_count;
         sp.outOnly = outOnly;
-        sp.kingKeys = ctx->dKingKeys;
-        sp.outKeys = ctx->dOutKeys;
+        sp.kingKeys = x.dKingKeys;
+        sp.outKeys = x.dOutKeys;
         if (n <= 1024 && !d_count) {  // single-launch path (kSmallSortMax): its own buffer, never needs clearing
-            sp.hist = ctx->dHist + 2 * kHistWords;
+            sp.hist = x.dHist + 2 * kHistWords;
             sp.histNext = sp.hist;
         } else {
-            sp.hist = ctx->dHist + kHistWords * ctx->histCur;
-            sp.histNext = ctx->dHist + kHistWords * (ctx->histCur ^ 1);
-            ctx->histCur ^= 1;
+            sp.hist = x.dHist + kHistWords * x.histCur;
+            sp.histNext = x.dHist + kHistWords * (x.histCur ^ 1);
+            x.histCur ^= 1;
         }
-        ctx->histUsed = sp.hist;
-        sp.perspOrder = ctx->dPerspOrder;
-        sp.posOrder = ctx->dPosOrder;
+        x.histUsed = sp.hist;
+        sp.perspOrder = x.dPerspOrder;
+        sp.posOrder = x.dPosOrder;
         SPX_HIP(launchSort(sp, s));
         return SPX_OK;
     }
     MlpParams mp{};
     mp.nPositions = uint32_t(n);
-    mp.posOrder = ctx->dPosOrder;
-    mp.hist = ctx->histUsed;
-    mp.ftOut = ctx->dFtOut;
+    mp.posOrder = x.dPosOrder;
+    mp.hist = x.histUsed;
+    mp.ftOut = x.dFtOut;
     mp.l1W = ctx->dL1W;
     mp.l1B = ctx->dL1B;
     mp.l2W = ctx->dL2W;
@@ -924,11 +935,11 @@ static hipError_t launchFullFt(const spx_ctx* ctx, const FtParams& fp, size_t nP
 }
 
 // MLP of a handful of positions without any sort: every position is its own tile and finds its bucket from its record
-static int runTinyMlp(spx_ctx* ctx, const void* d_records, size_t n, void* d_out, hipStream_t s) {
+static int runTinyMlp(const spx_ctx* ctx, const ScratchSet& x, const void* d_records, size_t n, void* d_out, hipStream_t s) {
     MlpParams mp{};
     mp.nPositions = uint32_t(n);
     mp.records = static_cast<const uint64_t*>(d_records);
-    mp.ftOut = ctx->dFtOut;
+    mp.ftOut = x.dFtOut;
     mp.l1W = ctx->dL1W;
     mp.l1B = ctx->dL1B;
     mp.l2W = ctx->dL2W;
@@ -1023,7 +1034,7 @@ static int calibrateHotRows(spx_ctx* ctx, FtxParams xp, hipStream_t s) {
     return SPX_OK;
 }
 
-// the column-sliced pipeline's table (per context) and scratch (per lane; `ctx->ftx` is the set swapped in): allocated on
+// the column-sliced pipeline's table (per context) and scratch (per scratch set): allocated on
 // first use; a context sized to fill the HBM that has no room for them keeps the one-kernel path (false)
 static bool ensureFtx(spx_ctx* ctx, FtxScratch& x, size_t passPositions, hipStream_t s) {
     if (!ctx->ftxEnabled || ctx->ftxUnavailable) return false;
@@ -1072,6 +1083,21 @@ static bool ensureFtx(spx_ctx* ctx, FtxScratch& x, size_t passPositions, hipStre
     return true;
 }
 
+// Which path a full refresh of n positions takes, before anything is allocated; `gated`: a call on a lane (its FT kernel chained to
+// the other lanes')
+struct Route {
+    bool tiny;    // a handful of positions: no sort launch, every position its own MLP tile
+    bool sliced;  // the column-sliced pipeline (spx_ftx.hip), if its table and scratch fit (ensureFtx)
+};
+static Route routeOf(const spx_ctx* ctx, size_t n, bool gated) {
+    // (pipelined calls gain from 6 Ki positions on, stream-ordered ones from 10 Ki: profiles/r06_sliced_pipeline_small_batches.txt)
+    const size_t sliceFrom = (gated && !ctx->ftxMinForced) ? std::min(ctx->ftxMin, kFtxMinPositionsPipelined) : ctx->ftxMin;
+    const bool ftx = n >= sliceFrom && ctx->ftxEnabled && !ctx->ftxUnavailable;
+    // (a pipelined call that reaches the pipeline's threshold takes the pipeline, whatever tiny_batch_max says)
+    const bool tiny = n <= ctx->tinyBatchMax && !(gated && ftx);
+    return {tiny, !tiny && ftx};
+}
+
 int spx_eval_full_device(spx_ctx* ctx, const void* d_positions, size_t n, void* d_out, void* stream) {
     if (!ctx || (n && (!d_positions || !d_out))) {
         setError("spx_eval_full_device: null argument");
@@ -1094,35 +1120,27 @@ int spx_eval_full_device(spx_ctx* ctx, const void* d_positions, size_t n, void* 
     }
     SPX_HIP(hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    hipEvent_t* ev = nullptr;
-    bool profiled = false;
-    if (ctx->profUsed + kProfEventsPerCall <= ctx->profEvents.size()) {
-        ev = &ctx->profEvents[ctx->profUsed];
-        ctx->profUsed += kProfEventsPerCall;
-        profiled = true;
-    } else if (ctx->paceEvents && ctx->paceEnabled) {
-        ev = ctx->paceEvents;
-    }
-    if (ev && (profiled || (ctx->paceMask >> 0 & 1u))) SPX_HIP(hipEventRecord(ev[0], s));
-    if (ev && !profiled) {
-        for (uint32_t r = 0; r < ctx->paceHeadExtra; ++r) SPX_HIP(hipEventRecord(ev[0], s));
-    }
+    ScratchSet& x = *ctx->active;
+    const CallGates& gates = ctx->gates;
+    const bool profiled = ctx->profUsed + kProfEventsPerCall <= ctx->profEvents.size();
+    hipEvent_t* ev = profiled ? &ctx->profEvents[ctx->profUsed] : gates.pace;
+    if (profiled) ctx->profUsed += kProfEventsPerCall;
+    // a profile's five events, or the lane's three pace records (spx_ctx::paceEnabled)
+    auto mark = [&](size_t k) { return ev && (profiled || k < 2) ? hipEventRecord(ev[k], s) : hipSuccess; };
+    SPX_HIP(mark(0));
+    if (!profiled) SPX_HIP(mark(0));
     // big batches: the column-sliced pipeline (spx_ftx.hip); it orders the perspectives itself, so only the MLP's
     // output-bucket order is sorted here
-    FtxScratch& scratch = ctx->ftx;
-    // (pipelined calls - a lane's gate is set - gain from 6 Ki positions on, stream-ordered ones from 10 Ki:
-    // profiles/r06_sliced_pipeline_small_batches.txt)
-    const size_t sliceFrom = (ctx->ftGateRecord && !ctx->ftxMinForced) ? std::min(ctx->ftxMin, kFtxMinPositionsPipelined) : ctx->ftxMin;
-    // a handful of positions: no sort launch, every position its own MLP tile (a pipelined call that reaches the pipeline's
-    // threshold takes the pipeline, whatever tiny_batch_max says)
-    const bool tiny = n <= ctx->tinyBatchMax && !(ctx->ftGateRecord && n >= sliceFrom && ctx->ftxEnabled && !ctx->ftxUnavailable);
-    const bool sliced = !tiny && n >= sliceFrom && ensureFtx(ctx, scratch, std::min(n, kFtxMaxPositions), s);
+    FtxScratch& scratch = x.ftx;
+    const Route route = routeOf(ctx, n, gates.record != nullptr);
+    const bool tiny = route.tiny;
+    const bool sliced = route.sliced && ensureFtx(ctx, scratch, std::min(n, kFtxMaxPositions), s);
     // a one-pass batch of the pipeline gets the MLP's output-bucket order from the pipeline's own sort (FtxParams::posOrder): no
     // spx_sort_* launches (option ftx_fold_sort = 0: as before)
     const bool foldSort = sliced && ctx->ftxFoldSort && n <= scratch.capacity;
-    int rc = (tiny || foldSort) ? SPX_OK : runSortAndMlp(ctx, d_positions, n, nullptr, s, false, nullptr, sliced);
+    int rc = (tiny || foldSort) ? SPX_OK : runSortAndMlp(ctx, x, d_positions, n, nullptr, s, false, nullptr, sliced);
     if (rc != SPX_OK) return rc;
-    if (ev && (profiled || (ctx->paceMask >> 1 & 1u))) SPX_HIP(hipEventRecord(ev[1], s));
+    SPX_HIP(mark(1));
     if (sliced) {
         // passes of at most the scratch's capacity; a pass's preparation (extraction, sort, plan) comes before the
         // pipelined calls' gate, so that it runs beside another batch's gather
@@ -1143,11 +1161,11 @@ int spx_eval_full_device(spx_ctx* ctx, const void* d_positions, size_t n, void* 
             xp.groupHead = scratch.groupHead;
             xp.stages = scratch.stages;
             xp.hiMask = ctx->dHiMask;
-            xp.ftOut = ctx->dFtOut + lo * size_t(kL1);
-            xp.posOrder = foldSort ? ctx->dPosOrder : nullptr;
+            xp.ftOut = x.dFtOut + lo * size_t(kL1);
+            xp.posOrder = foldSort ? x.dPosOrder : nullptr;
             xp.outCounts = scratch.outHist + kHistOut + 8;  // (the 8 words behind the counts the MLP reads)
             xp.mlpHist = scratch.outHist;
-            if (foldSort) ctx->histUsed = scratch.outHist;
+            if (foldSort) x.histUsed = scratch.outHist;
             if (!ctx->hotCalibrated && ctx->hotAutoCalibrate) {
                 // the first big batch of this context chooses the hot set: one extra extraction + a histogram, and the host WAITS for
                 // them (and for the context's other streams) inside this call. A stream that is being captured into a hipGraph must
@@ -1171,8 +1189,8 @@ int spx_eval_full_device(spx_ctx* ctx, const void* d_positions, size_t n, void* 
             // so far wrote is overwritten in stream order; the sort histogram a half-run preparation leaves behind is zeroed
             hipError_t launched = (ctx->ftxFailLaunch >= 0 && ctx->ftxFailLaunch-- == 0) ? hipErrorLaunchFailure : launchFtxPrepare(xp, s);
             if (launched == hipSuccess && lo == 0) {
-                if (ctx->ftGateWait) SPX_HIP(hipStreamWaitEvent(s, ctx->ftGateWait, 0));
-                if (ev && (profiled || (ctx->paceMask >> 4 & 1u))) SPX_HIP(hipEventRecord(ev[4], s));
+                if (gates.wait) SPX_HIP(hipStreamWaitEvent(s, gates.wait, 0));
+                SPX_HIP(mark(4));
             }
             if (launched == hipSuccess) launched = launchFtxGather(xp, s);
             if (launched != hipSuccess) {
@@ -1185,40 +1203,25 @@ int spx_eval_full_device(spx_ctx* ctx, const void* d_positions, size_t n, void* 
             }
         }
     } else {
-        if (ctx->ftGateWait) SPX_HIP(hipStreamWaitEvent(s, ctx->ftGateWait, 0));  // pipelined calls: FT kernels are chained
-        if (ev && (profiled || (ctx->paceMask >> 4 & 1u))) SPX_HIP(hipEventRecord(ev[4], s));  // after the wait: the FT interval is the kernel alone
+        if (gates.wait) SPX_HIP(hipStreamWaitEvent(s, gates.wait, 0));  // pipelined calls: FT kernels are chained
+        SPX_HIP(mark(4));  // after the wait: the FT interval is the kernel alone
         FtParams fp{};
         fp.positions = d_positions;
         fp.nPositions = uint32_t(n);
-        fp.order = (ctx->kingSortEnabled && !tiny) ? ctx->dPerspOrder : nullptr;
+        fp.order = (ctx->kingSortEnabled && !tiny) ? x.dPerspOrder : nullptr;
         fp.t = tablesOf(ctx);
-        fp.ftOut = ctx->dFtOut;
+        fp.ftOut = x.dFtOut;
         SPX_HIP(launchFullFt(ctx, fp, 2 * n, s));
     }
-    if (ctx->ftGateRecord) SPX_HIP(hipEventRecord(ctx->ftGateRecord, s));
-    if (ev && (profiled || (ctx->paceMask >> 2 & 1u))) SPX_HIP(hipEventRecord(ev[2], s));
-    rc = tiny ? runTinyMlp(ctx, d_positions, n, d_out, s) : runSortAndMlp(ctx, d_positions, n, d_out, s, true);
+    if (gates.record) SPX_HIP(hipEventRecord(gates.record, s));
+    SPX_HIP(mark(2));
+    rc = tiny ? runTinyMlp(ctx, x, d_positions, n, d_out, s) : runSortAndMlp(ctx, x, d_positions, n, d_out, s, true);
     if (rc != SPX_OK) return rc;
-    if (ev && (profiled || (ctx->paceMask >> 3 & 1u))) SPX_HIP(hipEventRecord(ev[3], s));
+    SPX_HIP(mark(3));
     return SPX_OK;
 }
 
 // ---- pipelined full-refresh evaluation ----
-static void swapLane(spx_ctx* ctx, spx_ctx::EvalLane& lane) {
-    std::swap(ctx->dFtOut, lane.dFtOut);
-    std::swap(ctx->dKingKeys, lane.dKingKeys);
-    std::swap(ctx->dOutKeys, lane.dOutKeys);
-    std::swap(ctx->dStaged, lane.dStaged);
-    std::swap(ctx->dHist, lane.dHist);
-    std::swap(ctx->dPerspOrder, lane.dPerspOrder);
-    std::swap(ctx->dPosOrder, lane.dPosOrder);
-    std::swap(ctx->dRefreshList, lane.dRefreshList);
-    std::swap(ctx->histUsed, lane.histUsed);
-    std::swap(ctx->histCur, lane.histCur);
-    std::swap(ctx->refreshCur, lane.refreshCur);
-    std::swap(ctx->ftx, lane.ftx);
-}
-
 static int ensureLanes(spx_ctx* ctx) {
     if (ctx->lanesReady) return SPX_OK;
     // The two lanes must sit on different hardware queues or their kernels serialise: HIP spreads streams of one
@@ -1227,15 +1230,8 @@ static int ensureLanes(spx_ctx* ctx) {
     SPX_HIP(hipDeviceGetStreamPriorityRange(&leastPriority, &greatestPriority));
     int laneIndex = 0;
     for (auto& lane : ctx->lanes) {
-        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&lane.dFtOut), ctx->maxBatch * size_t(kL1)));
-        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&lane.dKingKeys), ctx->maxBatch * 2));
-        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&lane.dOutKeys), ctx->maxBatch));
-        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&lane.dStaged), ctx->maxBatch * 32));
-        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&lane.dHist), (3 * kHistWords + 64) * sizeof(uint32_t)));
-        SPX_HIP(hipMemset(lane.dHist, 0, (3 * kHistWords + 64) * sizeof(uint32_t)));
-        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&lane.dPerspOrder), ctx->maxBatch * 2 * sizeof(uint32_t)));
-        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&lane.dPosOrder), ctx->maxBatch * sizeof(uint32_t)));
-        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&lane.dRefreshList), ctx->maxBatch * 2 * sizeof(uint32_t)));
+        const int rc = lane.set.allocate(ctx->maxBatch);
+        if (rc != SPX_OK) return rc;
         // (lanes 0 / 1: the two ends of the range; lane 2: the level between them, where the device has one)
         const int priority = laneIndex == 0 ? leastPriority : (laneIndex == 1 ? greatestPriority : (leastPriority + greatestPriority) / 2);
         ++laneIndex;
@@ -1249,24 +1245,47 @@ static int ensureLanes(spx_ctx* ctx) {
     return SPX_OK;
 }
 
-static void releaseLanes(spx_ctx* ctx) {
-    for (auto& lane : ctx->lanes) {
-        if (lane.stream) (void)hipStreamSynchronize(lane.stream);
-        void* lanePtrs[] = {lane.dFtOut, lane.dKingKeys, lane.dOutKeys, lane.dStaged, lane.dHist, lane.dPerspOrder,
-                            lane.dPosOrder, lane.dRefreshList, lane.dIn, lane.dOutStage};
-        for (void* q : lanePtrs) {
-            if (q) (void)hipFree(q);
-        }
-        lane.ftx.release();
-        if (lane.hIn) (void)hipHostFree(lane.hIn);
-        if (lane.hOut) (void)hipHostFree(lane.hOut);
-        if (lane.ftDone) (void)hipEventDestroy(lane.ftDone);
-        if (lane.done) (void)hipEventDestroy(lane.done);
-        if (lane.stream) (void)hipStreamDestroy(lane.stream);
-        lane = spx_ctx::EvalLane{};
-    }
+// false: the lanes do not fit into the device memory (a context sized to fill the HBM). The first failure gives them up for good:
+// from then on the calls that would use them run stream-ordered on the context's own stream - same results.
+static bool lanesUsable(spx_ctx* ctx) {
+    if (ctx->lanesUnavailable) return false;
+    if (ensureLanes(ctx) == SPX_OK) return true;
+    (void)hipGetLastError();
+    for (auto& lane : ctx->lanes) lane.release();
     ctx->lanesReady = false;
+    ctx->lanesUnavailable = true;
+    return false;
 }
+
+// the done event of a pipelined call that ran stream-ordered (lanesUsable: false)
+static int recordFallbackDone(spx_ctx* ctx, void** done_event) {
+    if (!ctx->fallbackDone) SPX_HIP(hipEventCreateWithFlags(&ctx->fallbackDone, hipEventDisableTiming));
+    SPX_HIP(hipEventRecord(ctx->fallbackDone, ctx->stream));
+    if (done_event) *done_event = ctx->fallbackDone;
+    return SPX_OK;
+}
+
+// The calls between enterLane and leaveLane use the lane's scratch set; with `gates`, their big kernel waits for the one `other`
+// recorded last and signals the lane's own; with `pace`, an unprofiled call records the lane's pace events.
+static void enterLane(spx_ctx* ctx, spx_ctx::EvalLane& lane, const spx_ctx::EvalLane& other, bool gates, bool pace) {
+    ctx->active = &lane.set;
+    ctx->gates.wait = (gates && other.ftRecorded) ? other.ftDone : nullptr;
+    ctx->gates.record = gates ? lane.ftDone : nullptr;
+    ctx->gates.pace = pace ? lane.pace : nullptr;
+}
+
+static void leaveLane(spx_ctx* ctx) {
+    ctx->active = &ctx->own;
+    ctx->gates = CallGates{};
+}
+
+struct LaneScope {  // a gated call on a lane
+    spx_ctx* ctx;
+    LaneScope(spx_ctx* c, spx_ctx::EvalLane& lane, const spx_ctx::EvalLane& other, bool pace) : ctx(c) {
+        enterLane(ctx, lane, other, true, pace);
+    }
+    ~LaneScope() { leaveLane(ctx); }
+};
 
 int spx_eval_full_device_async(spx_ctx* ctx, const void* d_positions, size_t n, void* d_out, void** done_event) {
     if (!ctx) {
@@ -1274,21 +1293,9 @@ int spx_eval_full_device_async(spx_ctx* ctx, const void* d_positions, size_t n, 
         return SPX_ERR_INVALID_ARG;
     }
     SPX_HIP(hipSetDevice(ctx->device));
-    int rc = ctx->lanesUnavailable ? SPX_ERR_HIP : ensureLanes(ctx);
-    if (rc != SPX_OK) {
-        // no room for a second scratch set (a context sized to fill the HBM): same results, stream-ordered on the
-        // context's own stream
-        if (!ctx->lanesUnavailable) {
-            (void)hipGetLastError();
-            releaseLanes(ctx);
-            ctx->lanesUnavailable = true;
-            if (!ctx->fallbackDone) SPX_HIP(hipEventCreateWithFlags(&ctx->fallbackDone, hipEventDisableTiming));
-        }
-        rc = spx_eval_full_device(ctx, d_positions, n, d_out, ctx->stream);
-        if (rc != SPX_OK) return rc;
-        SPX_HIP(hipEventRecord(ctx->fallbackDone, ctx->stream));
-        if (done_event) *done_event = ctx->fallbackDone;
-        return SPX_OK;
+    if (!lanesUsable(ctx)) {
+        const int rc = spx_eval_full_device(ctx, d_positions, n, d_out, ctx->stream);
+        return rc != SPX_OK ? rc : recordFallbackDone(ctx, done_event);
     }
     if (n > ctx->callLimit) {
         setError("batch of " + std::to_string(n) + " exceeds context capacity " + std::to_string(ctx->callLimit));
@@ -1307,15 +1314,9 @@ int spx_eval_full_device_async(spx_ctx* ctx, const void* d_positions, size_t n, 
         spx_ctx::EvalLane& lane = ctx->lanes[li];
         spx_ctx::EvalLane& other = ctx->lanes[(li + nLanes - 1) % nLanes];
         ctx->laneNext = (ctx->laneNext + 1) % 6;
-        swapLane(ctx, lane);
-        ctx->ftGateWait = other.ftRecorded ? other.ftDone : nullptr;
-        ctx->ftGateRecord = lane.ftDone;
-        ctx->paceEvents = lane.pace;
-        rc = spx_eval_full_device(ctx, static_cast<const char*>(d_positions) + lo * sizeof(spx_packed_pos), m,
-                                  static_cast<int32_t*>(d_out) + lo, lane.stream);
-        ctx->ftGateWait = ctx->ftGateRecord = nullptr;
-        ctx->paceEvents = nullptr;
-        swapLane(ctx, lane);
+        const LaneScope on(ctx, lane, other, ctx->paceEnabled);
+        const int rc = spx_eval_full_device(ctx, static_cast<const char*>(d_positions) + lo * sizeof(spx_packed_pos), m,
+                                            static_cast<int32_t*>(d_out) + lo, lane.stream);
         if (rc != SPX_OK) return rc;
         if (m) lane.ftRecorded = true;
         if (last) SPX_HIP(hipStreamWaitEvent(lane.stream, last->done, 0));  // `done` of the call covers every chunk
@@ -1350,10 +1351,7 @@ int ctxLaneBegin(spx_ctx* ctx, int laneIndex, void** stream, bool gates) {
     const int rc = ensureLanes(ctx);
     if (rc != SPX_OK) return rc;
     spx_ctx::EvalLane& lane = ctx->lanes[laneIndex & 1];
-    spx_ctx::EvalLane& other = ctx->lanes[(laneIndex & 1) ^ 1];
-    swapLane(ctx, lane);
-    ctx->ftGateWait = (gates && other.ftRecorded) ? other.ftDone : nullptr;
-    ctx->ftGateRecord = gates ? lane.ftDone : nullptr;
+    enterLane(ctx, lane, ctx->lanes[(laneIndex & 1) ^ 1], gates, false);
     if (gates) lane.ftRecorded = true;  // conservatively: an unrecorded event counts as complete for hipStreamWaitEvent
     // an ungated lane may be under stream capture: spx_profile_* timing events have no place in a graph (a profile that was
     // left open ends here)
@@ -1362,9 +1360,8 @@ int ctxLaneBegin(spx_ctx* ctx, int laneIndex, void** stream, bool gates) {
     return SPX_OK;
 }
 
-void ctxLaneEnd(spx_ctx* ctx, int laneIndex) {
-    ctx->ftGateWait = ctx->ftGateRecord = nullptr;
-    swapLane(ctx, ctx->lanes[laneIndex & 1]);
+void ctxLaneEnd(spx_ctx* ctx, int /*laneIndex*/) {
+    leaveLane(ctx);
 }
 }  // namespace spx
 
@@ -1432,12 +1429,13 @@ int spx_acc_refresh_device(spx_ctx* ctx, const void* d_positions, const void* d_
     int rc = checkAcc(ctx, n, "spx_acc_refresh_device");
     if (rc != SPX_OK || n == 0) return rc;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    rc = runSortAndMlp(ctx, d_positions, n, nullptr, s, false);
+    ScratchSet& x = *ctx->active;
+    rc = runSortAndMlp(ctx, x, d_positions, n, nullptr, s, false);
     if (rc != SPX_OK) return rc;
     FtParams fp{};
     fp.positions = d_positions;
     fp.nPositions = uint32_t(n);
-    fp.order = ctx->kingSortEnabled ? ctx->dPerspOrder : nullptr;
+    fp.order = ctx->kingSortEnabled ? x.dPerspOrder : nullptr;
     fp.t = tablesOf(ctx);
     fp.ftOut = nullptr;
     fp.accOut = ctx->dArena;
@@ -1447,7 +1445,7 @@ int spx_acc_refresh_device(spx_ctx* ctx, const void* d_positions, const void* d_
     return SPX_OK;
 }
 
-static int launchUpdateAndRefresh(spx_ctx* ctx, UpdateParams& up, size_t n, hipStream_t s);
+static int launchUpdateAndRefresh(const spx_ctx* ctx, ScratchSet& x, UpdateParams& up, size_t n, hipStream_t s);
 
 int spx_acc_update_device(spx_ctx* ctx, const void* d_parent_slots, const void* d_child_slots,
                           const void* d_child_positions, size_t n, void* stream) {
@@ -1466,21 +1464,20 @@ int spx_acc_update_device(spx_ctx* ctx, const void* d_parent_slots, const void* 
     up.t = tablesOf(ctx);
     up.arena = ctx->dArena;
     up.slotRecords = ctx->dSlotRecords;
-    return launchUpdateAndRefresh(ctx, up, n, s);
+    return launchUpdateAndRefresh(ctx, *ctx->active, up, n, s);
 }
 
-static int updateEvalDevice(spx_ctx* ctx, const void* d_parent_slots, const void* d_child_slots,
-                            const void* d_child_positions, size_t n, const uint32_t* d_count, void* d_out, void* stream,
-                            const char* who);
+static int updateEvalDevice(spx_ctx* ctx, ScratchSet& x, const void* d_parent_slots, const void* d_child_slots,
+                            const void* d_child_positions, size_t n, const uint32_t* d_count, void* d_out, void* stream);
 
 // The update kernel proper, followed (second-generation kernel) by the pass that rebuilds the perspectives it deferred:
-// the feature-transformer kernel over the refresh list (ids in the context's dRefreshList, the count in one of two alternating
+// the feature-transformer kernel over the refresh list (ids in the scratch set's dRefreshList, the count in one of two alternating
 // device words behind the sort histograms; the pass clears the other one for the next update).
-static int launchUpdateAndRefresh(spx_ctx* ctx, UpdateParams& up, size_t n, hipStream_t s) {
+static int launchUpdateAndRefresh(const spx_ctx* ctx, ScratchSet& x, UpdateParams& up, size_t n, hipStream_t s) {
     const bool split = n <= ctx->updateSplitMaxV2;  // one wave per (record, perspective)
-    uint32_t* counters = ctx->dHist + 3 * kHistWords;
-    up.refreshList = ctx->dRefreshList;
-    up.refreshCount = counters + ctx->refreshCur;
+    uint32_t* counters = x.dHist + 3 * kHistWords;
+    up.refreshList = x.dRefreshList;
+    up.refreshCount = counters + x.refreshCur;
     // streaming (non-temporal) arena accesses only where accumulators are written: eval-only children keep cached parents
     const bool streamAcc = n >= ctx->streamAccMin && up.childSlots != nullptr;
     if (n <= ctx->updateChainMax && !up.nRecordsPtr) {
@@ -1507,13 +1504,13 @@ static int launchUpdateAndRefresh(spx_ctx* ctx, UpdateParams& up, size_t n, hipS
     fp.nPositions = uint32_t(n);
     fp.order = up.refreshList;
     fp.nPerspPtr = up.refreshCount;
-    fp.clearWord = counters + (ctx->refreshCur ^ 1);
+    fp.clearWord = counters + (x.refreshCur ^ 1);
     fp.t = up.t;
     fp.ftOut = up.ftOut;
     fp.accOut = up.childSlots ? up.arena : nullptr;  // eval-only children: rebuilt perspectives leave through ftOut alone
     fp.slots = up.childSlots;
     fp.slotRecords = up.slotRecords;
-    ctx->refreshCur ^= 1;
+    x.refreshCur ^= 1;
     // one wave per deferred perspective: ~n / 15 of them in play, grid-stride beyond. (One WORKGROUP per perspective - the team
     // kernel - was measured here and loses: 4 456 items are more than the resident workgroups, so the pass runs in rounds and
     // pays table staging and list building four times over: update + rebuild 0.291 -> 0.319 ms per 65 536-record ply,
@@ -1529,8 +1526,8 @@ static int launchUpdateAndRefresh(spx_ctx* ctx, UpdateParams& up, size_t n, hipS
 
 int spx_acc_update_eval_device(spx_ctx* ctx, const void* d_parent_slots, const void* d_child_slots,
                                const void* d_child_positions, size_t n, void* d_out, void* stream) {
-    return updateEvalDevice(ctx, d_parent_slots, d_child_slots, d_child_positions, n, nullptr, d_out, stream,
-                            "spx_acc_update_eval_device");
+    const int rc = checkAcc(ctx, n, "spx_acc_update_eval_device");
+    return rc != SPX_OK ? rc : updateEvalDevice(ctx, *ctx->active, d_parent_slots, d_child_slots, d_child_positions, n, nullptr, d_out, stream);
 }
 
 int spx_acc_update_eval_device_counted(spx_ctx* ctx, const void* d_parent_slots, const void* d_child_slots,
@@ -1540,15 +1537,15 @@ int spx_acc_update_eval_device_counted(spx_ctx* ctx, const void* d_parent_slots,
         setError("spx_acc_update_eval_device_counted: null count");
         return SPX_ERR_INVALID_ARG;
     }
-    return updateEvalDevice(ctx, d_parent_slots, d_child_slots, d_child_positions, capacity,
-                            static_cast<const uint32_t*>(d_count), d_out, stream, "spx_acc_update_eval_device_counted");
+    const int rc = checkAcc(ctx, capacity, "spx_acc_update_eval_device_counted");
+    return rc != SPX_OK ? rc : updateEvalDevice(ctx, *ctx->active, d_parent_slots, d_child_slots, d_child_positions, capacity,
+                                                static_cast<const uint32_t*>(d_count), d_out, stream);
 }
 
-static int updateEvalDevice(spx_ctx* ctx, const void* d_parent_slots, const void* d_child_slots,
-                            const void* d_child_positions, size_t n, const uint32_t* d_count, void* d_out, void* stream,
-                            const char* who) {
-    int rc = checkAcc(ctx, n, who);
-    if (rc != SPX_OK || n == 0) return rc;
+// (the caller has checked the context: checkAcc)
+static int updateEvalDevice(spx_ctx* ctx, ScratchSet& x, const void* d_parent_slots, const void* d_child_slots,
+                            const void* d_child_positions, size_t n, const uint32_t* d_count, void* d_out, void* stream) {
+    if (n == 0) return SPX_OK;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     UpdateParams up{};
     up.nRecords = uint32_t(n);
@@ -1559,9 +1556,9 @@ static int updateEvalDevice(spx_ctx* ctx, const void* d_parent_slots, const void
     up.t = tablesOf(ctx);
     up.arena = ctx->dArena;
     up.slotRecords = ctx->dSlotRecords;
-    up.ftOut = ctx->dFtOut;          // activations of the children straight from the update kernel's registers
-    up.stagedRecords = ctx->dStaged;
-    if (ctx->ftGateWait) SPX_HIP(hipStreamWaitEvent(s, ctx->ftGateWait, 0));  // lanes: the big kernels are chained
+    up.ftOut = x.dFtOut;          // activations of the children straight from the update kernel's registers
+    up.stagedRecords = x.dStaged;
+    if (ctx->gates.wait) SPX_HIP(hipStreamWaitEvent(s, ctx->gates.wait, 0));  // lanes: the big kernels are chained
     // spx_profile_*: the "ft" interval is the update kernel + its rebuild pass, the "mlp" interval the sort + MLP
     hipEvent_t* ev = nullptr;
     if (ctx->profUsed + kProfEventsPerCall <= ctx->profEvents.size()) {
@@ -1571,16 +1568,16 @@ static int updateEvalDevice(spx_ctx* ctx, const void* d_parent_slots, const void
         SPX_HIP(hipEventRecord(ev[1], s));
         SPX_HIP(hipEventRecord(ev[4], s));
     }
-    rc = launchUpdateAndRefresh(ctx, up, n, s);
+    int rc = launchUpdateAndRefresh(ctx, x, up, n, s);
     if (rc != SPX_OK) return rc;
-    if (ctx->ftGateRecord) SPX_HIP(hipEventRecord(ctx->ftGateRecord, s));
+    if (ctx->gates.record) SPX_HIP(hipEventRecord(ctx->gates.record, s));
     if (ev) SPX_HIP(hipEventRecord(ev[2], s));
     if (!d_count && n <= ctx->tinyBatchMax) {
-        rc = runTinyMlp(ctx, ctx->dStaged, n, d_out, s);
+        rc = runTinyMlp(ctx, x, x.dStaged, n, d_out, s);
     } else {
-        rc = runSortAndMlp(ctx, ctx->dStaged, n, nullptr, s, false, d_count, true);
+        rc = runSortAndMlp(ctx, x, x.dStaged, n, nullptr, s, false, d_count, true);
         if (rc != SPX_OK) return rc;
-        rc = runSortAndMlp(ctx, ctx->dStaged, n, d_out, s, true, d_count);
+        rc = runSortAndMlp(ctx, x, x.dStaged, n, d_out, s, true, d_count);
     }
     if (rc != SPX_OK) return rc;
     if (ev) SPX_HIP(hipEventRecord(ev[3], s));
@@ -1812,31 +1809,15 @@ int spx_acc_update_eval_device_async(spx_ctx* ctx, const void* d_parent_slots, c
                                      const void* d_child_positions, size_t n, void* d_out, void** done_event) {
     int rc = checkAcc(ctx, n, "spx_acc_update_eval_device_async");
     if (rc != SPX_OK) return rc;
-    rc = ctx->lanesUnavailable ? SPX_ERR_HIP : ensureLanes(ctx);
-    if (rc != SPX_OK) {  // no room for the second scratch set: same results, stream-ordered on the context's own stream
-        if (!ctx->lanesUnavailable) {
-            (void)hipGetLastError();
-            releaseLanes(ctx);
-            ctx->lanesUnavailable = true;
-            if (!ctx->fallbackDone) SPX_HIP(hipEventCreateWithFlags(&ctx->fallbackDone, hipEventDisableTiming));
-        }
-        rc = updateEvalDevice(ctx, d_parent_slots, d_child_slots, d_child_positions, n, nullptr, d_out, ctx->stream,
-                              "spx_acc_update_eval_device_async");
-        if (rc != SPX_OK) return rc;
-        SPX_HIP(hipEventRecord(ctx->fallbackDone, ctx->stream));
-        if (done_event) *done_event = ctx->fallbackDone;
-        return SPX_OK;
+    if (!lanesUsable(ctx)) {
+        rc = updateEvalDevice(ctx, ctx->own, d_parent_slots, d_child_slots, d_child_positions, n, nullptr, d_out, ctx->stream);
+        return rc != SPX_OK ? rc : recordFallbackDone(ctx, done_event);
     }
     spx_ctx::EvalLane& lane = ctx->lanes[ctx->laneNext & 1];
     spx_ctx::EvalLane& other = ctx->lanes[(ctx->laneNext & 1) ^ 1];
     ++ctx->laneNext;
-    swapLane(ctx, lane);
-    ctx->ftGateWait = other.ftRecorded ? other.ftDone : nullptr;
-    ctx->ftGateRecord = lane.ftDone;
-    rc = updateEvalDevice(ctx, d_parent_slots, d_child_slots, d_child_positions, n, nullptr, d_out, lane.stream,
-                          "spx_acc_update_eval_device_async");
-    ctx->ftGateWait = ctx->ftGateRecord = nullptr;
-    swapLane(ctx, lane);
+    const LaneScope on(ctx, lane, other, false);
+    rc = updateEvalDevice(ctx, lane.set, d_parent_slots, d_child_slots, d_child_positions, n, nullptr, d_out, lane.stream);
     if (rc != SPX_OK) return rc;
     if (n) lane.ftRecorded = true;
     SPX_HIP(hipEventRecord(lane.done, lane.stream));
@@ -1861,15 +1842,16 @@ int spx_acc_update_observed_device(spx_ctx* ctx, const void* d_parent_slots, con
     up.arena = ctx->dArena;
     up.slotRecords = ctx->dSlotRecords;
     up.deltas = static_cast<const uint8_t*>(d_deltas);
+    ScratchSet& x = *ctx->active;
     if (d_out) {
-        up.ftOut = ctx->dFtOut;
-        up.stagedRecords = ctx->dStaged;
+        up.ftOut = x.dFtOut;
+        up.stagedRecords = x.dStaged;
     }
     SPX_HIP(launchUpdateObserved(up, ftGrid(ctx, 2 * n), s));  // one wave per (record, perspective)
     if (!d_out) return SPX_OK;
-    rc = runSortAndMlp(ctx, ctx->dStaged, n, nullptr, s, false, nullptr, true);
+    rc = runSortAndMlp(ctx, x, x.dStaged, n, nullptr, s, false, nullptr, true);
     if (rc != SPX_OK) return rc;
-    return runSortAndMlp(ctx, ctx->dStaged, n, d_out, s, true);
+    return runSortAndMlp(ctx, x, x.dStaged, n, d_out, s, true);
 }
 
 int spx_acc_update_observed(spx_ctx* ctx, const uint32_t* parent_slots, const uint32_t* child_slots,
@@ -1909,15 +1891,16 @@ int spx_acc_eval_device(spx_ctx* ctx, const void* d_slots, size_t n, void* d_out
     ap.slots = static_cast<const uint32_t*>(d_slots);
     ap.arena = ctx->dArena;
     ap.slotRecords = ctx->dSlotRecords;
-    ap.ftOut = ctx->dFtOut;
-    ap.stagedRecords = ctx->dStaged;
+    ScratchSet& x = *ctx->active;
+    ap.ftOut = x.dFtOut;
+    ap.stagedRecords = x.dStaged;
     uint32_t blocks = uint32_t((n + 3) / 4);
     if (blocks > ctx->ftGridCap) blocks = ctx->ftGridCap;
     SPX_HIP(launchSlotAct(ap, blocks, s));
-    if (n <= ctx->tinyBatchMax) return runTinyMlp(ctx, ctx->dStaged, n, d_out, s);
-    rc = runSortAndMlp(ctx, ctx->dStaged, n, nullptr, s, false, nullptr, true);
+    if (n <= ctx->tinyBatchMax) return runTinyMlp(ctx, x, x.dStaged, n, d_out, s);
+    rc = runSortAndMlp(ctx, x, x.dStaged, n, nullptr, s, false, nullptr, true);
     if (rc != SPX_OK) return rc;
-    return runSortAndMlp(ctx, ctx->dStaged, n, d_out, s, true);
+    return runSortAndMlp(ctx, x, x.dStaged, n, d_out, s, true);
 }
 
 static int checkSlots(const spx_ctx* ctx, const uint32_t* slots, size_t n, const char* who) {
@@ -2048,13 +2031,14 @@ int spx_acc_update_chain_eval(spx_ctx* ctx, uint32_t parent_slot, const uint32_t
     cp.t = tablesOf(ctx);
     cp.arena = ctx->dArena;
     cp.slotRecords = ctx->dSlotRecords;
+    const ScratchSet& x = *ctx->active;
     if (out) {
-        cp.ftOut = ctx->dFtOut;
-        cp.stagedRecords = ctx->dStaged;
+        cp.ftOut = x.dFtOut;
+        cp.stagedRecords = x.dStaged;
     }
     SPX_HIP(launchUpdateChain(cp, ctx->stream));
     if (out) {
-        rc = runTinyMlp(ctx, ctx->dStaged, 1, dBase + offScores, ctx->stream);
+        rc = runTinyMlp(ctx, x, x.dStaged, 1, dBase + offScores, ctx->stream);
         if (rc != SPX_OK) return rc;
     }
     SPX_HIP(hipStreamSynchronize(ctx->stream));
@@ -2108,10 +2092,9 @@ int spx_profile_begin(spx_ctx* ctx, size_t max_calls) {
 }
 
 int spx_ctx_sliced_ft(const spx_ctx* ctx, size_t n) {
-    if (!ctx || !ctx->ftxEnabled || ctx->ftxUnavailable || n <= ctx->tinyBatchMax) return 0;
-    // (per chunk of a call; pipelined calls of a context whose lanes did not fit run stream-ordered: the same threshold then)
-    const size_t pipelinedFrom = (ctx->ftxMinForced || ctx->lanesUnavailable) ? ctx->ftxMin : std::min(ctx->ftxMin, kFtxMinPositionsPipelined);
-    return (n >= ctx->ftxMin ? 1 : 0) | (n >= pipelinedFrom ? 2 : 0);
+    if (!ctx) return 0;
+    // (per chunk of a call; pipelined calls of a context whose lanes did not fit run stream-ordered)
+    return (routeOf(ctx, n, false).sliced ? 1 : 0) | (routeOf(ctx, n, !ctx->lanesUnavailable).sliced ? 2 : 0);
 }
 
 int spx_ctx_calibrate(spx_ctx* ctx, const void* d_positions, size_t n) {
@@ -2121,14 +2104,15 @@ int spx_ctx_calibrate(spx_ctx* ctx, const void* d_positions, size_t n) {
     }
     SPX_HIP(hipSetDevice(ctx->device));
     const size_t m = std::min({n, ctx->maxBatch, kFtxMaxPositions});
-    if (!m || !ensureFtx(ctx, ctx->ftx, m, ctx->stream)) return SPX_OK;  // (no pipeline on this context: nothing to choose)
+    FtxScratch& x = ctx->active->ftx;
+    if (!m || !ensureFtx(ctx, x, m, ctx->stream)) return SPX_OK;  // (no pipeline on this context: nothing to choose)
     FtxParams xp{};
     xp.positions = d_positions;
     xp.nPositions = uint32_t(m);
     xp.t = tablesOf(ctx);
     xp.rowS = ctx->dRowS;
-    xp.lists = ctx->ftx.lists;
-    xp.heads = ctx->ftx.heads;
+    xp.lists = x.lists;
+    xp.heads = x.heads;
     return calibrateHotRows(ctx, xp, ctx->stream);
 }
 
@@ -2278,12 +2262,7 @@ int spx_eval_full(spx_ctx* ctx, const spx_packed_pos* positions, size_t n, int32
         std::memcpy(out, scores, n * sizeof(int32_t));
         return SPX_OK;
     }
-    if (n > ctx->maxBatch && !ctx->lanesUnavailable && ensureLanes(ctx) != SPX_OK) {
-        (void)hipGetLastError();  // no room for the lanes: plain chunk loop below
-        releaseLanes(ctx);
-        ctx->lanesUnavailable = true;
-    }
-    if (n > ctx->maxBatch && !ctx->lanesUnavailable) {
+    if (n > ctx->maxBatch && lanesUsable(ctx)) {
         // More than one chunk of the context's capacity (rescoring a data set): the chunks alternate between the two
         // lanes - while one chunk is evaluated, the next is copied into page-locked staging and sent over PCIe and the
         // previous one's scores come back; FT kernels chained as in spx_eval_full_device_async.
@@ -2314,13 +2293,8 @@ int spx_eval_full(spx_ctx* ctx, const spx_packed_pos* positions, size_t n, int32
             spx_ctx::EvalLane& other = ctx->lanes[li ^ 1];
             std::memcpy(lane.hIn, positions + lo, m * sizeof(spx_packed_pos));
             SPX_HIP(hipMemcpyAsync(lane.dIn, lane.hIn, m * sizeof(spx_packed_pos), hipMemcpyHostToDevice, lane.stream));
-            swapLane(ctx, lane);
-            ctx->ftGateWait = other.ftRecorded ? other.ftDone : nullptr;
-            ctx->ftGateRecord = lane.ftDone;
-            rc = spx_eval_full_device(ctx, lane.dIn, m, lane.dOutStage, lane.stream);
-            ctx->ftGateWait = ctx->ftGateRecord = nullptr;
-            swapLane(ctx, lane);
-            if (rc != SPX_OK) return rc;
+            const LaneScope on(ctx, lane, other, false);
+            if ((rc = spx_eval_full_device(ctx, lane.dIn, m, lane.dOutStage, lane.stream)) != SPX_OK) return rc;
             lane.ftRecorded = true;
             SPX_HIP(hipMemcpyAsync(lane.hOut, lane.dOutStage, m * sizeof(int32_t), hipMemcpyDeviceToHost, lane.stream));
             SPX_HIP(hipEventRecord(lane.done, lane.stream));
@@ -2430,7 +2404,7 @@ int spx_debug_copy_ft(spx_ctx* ctx, size_t n, uint8_t* out) {
     }
     SPX_HIP(hipSetDevice(ctx->device));
     SPX_HIP(hipDeviceSynchronize());
-    SPX_HIP(hipMemcpy(out, ctx->dFtOut, n * size_t(kL1), hipMemcpyDeviceToHost));
+    SPX_HIP(hipMemcpy(out, ctx->active->dFtOut, n * size_t(kL1), hipMemcpyDeviceToHost));
     return SPX_OK;
 }
 
@@ -2441,7 +2415,7 @@ int spx_debug_ftx_block_times(spx_ctx* ctx, int slot, uint64_t* out) {
         setError("spx_debug_ftx_block_times: invalid argument");
         return SPX_ERR_INVALID_ARG;
     }
-    const FtxScratch& x = slot < 0 ? ctx->ftx : ctx->lanes[slot].ftx;
+    const FtxScratch& x = slot < 0 ? ctx->own.ftx : ctx->lanes[slot].set.ftx;
     if (!x.plan) {
         setError("spx_debug_ftx_block_times: that scratch set was never used");
         return SPX_ERR_INVALID_ARG;
@@ -2462,7 +2436,7 @@ int spx_debug_ftx_walk(spx_ctx* ctx, int slot, uint32_t* out) {
         setError("spx_debug_ftx_walk: invalid argument");
         return SPX_ERR_INVALID_ARG;
     }
-    const FtxScratch& x = slot < 0 ? ctx->ftx : ctx->lanes[slot].ftx;
+    const FtxScratch& x = slot < 0 ? ctx->own.ftx : ctx->lanes[slot].set.ftx;
     if (!x.plan) {
         setError("spx_debug_ftx_walk: that scratch set was never used");
         return SPX_ERR_INVALID_ARG;
@@ -2514,7 +2488,7 @@ int spx_debug_ftx_lists(spx_ctx* ctx, int slot, size_t n, uint32_t* counts, uint
         setError("spx_debug_ftx_lists: invalid argument");
         return SPX_ERR_INVALID_ARG;
     }
-    const FtxScratch& x = slot < 0 ? ctx->ftx : ctx->lanes[slot].ftx;
+    const FtxScratch& x = slot < 0 ? ctx->own.ftx : ctx->lanes[slot].set.ftx;
     if (!x.lists || n > x.capacity) {
         setError("spx_debug_ftx_lists: that scratch set was never used (or holds fewer positions)");
         return SPX_ERR_INVALID_ARG;
@@ -2564,7 +2538,7 @@ int spx_debug_ftx_plan(spx_ctx* ctx, int slot, uint32_t* out) {
         setError("spx_debug_ftx_plan: invalid argument");
         return SPX_ERR_INVALID_ARG;
     }
-    const FtxScratch& x = slot < 0 ? ctx->ftx : ctx->lanes[slot].ftx;
+    const FtxScratch& x = slot < 0 ? ctx->own.ftx : ctx->lanes[slot].set.ftx;
     if (!x.plan) {
         setError("spx_debug_ftx_plan: that scratch set was never used");
         return SPX_ERR_INVALID_ARG;

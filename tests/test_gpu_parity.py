@@ -478,9 +478,14 @@ def test_column_sliced_pipeline_equals_the_kernel_and_the_oracle(sp, oracle, net
     blob = net_blob(preset)
     pos = sp.random_positions(70001, seed=909, min_ply=0, max_ply=160, dfrc_every=3)
     with sp.NnueState(sp.Network(blob), device=0, max_batch=1 << 17, sliced_ft=False) as plain, \
-            _state_with_options(sp, blob, {"ftx_min": 8200}, max_batch=1 << 17) as sliced:
+            _state_with_options(sp, blob, {"ftx_min": 8200}, max_batch=1 << 17) as sliced, \
+            sp.NnueState(sp.Network(blob), device=0, max_batch=8192) as default:
         assert not plain.takes_sliced_pipeline(70001) and sliced.takes_sliced_pipeline(8200) and not sliced.takes_sliced_pipeline(8199)
         assert not plain.takes_sliced_pipeline(70001, pipelined=True) and sliced.takes_sliced_pipeline(8200, pipelined=True)
+        # default options: pipelined calls take the pipeline from 6 144 positions on, below the tiny-batch limit too
+        for n in (6144, 8192):
+            assert default.takes_sliced_pipeline(n, pipelined=True) and not default.takes_sliced_pipeline(n)
+        assert not default.takes_sliced_pipeline(6143, pipelined=True)
         want = plain.evaluate_once(pos)
         oracle.use(blob, preset)
         mail, stm = sp.positions_to_mailboxes(pos[:3000])
