@@ -225,6 +225,31 @@ int spx_ctx_synchronize(spx_ctx* ctx);
 /* spx_acc_reserve sizes the arena (never shrinks). Growing it keeps every materialised slot: accumulators and records are
  * copied into the new allocation (both arenas exist for the duration of the call). */
 int spx_acc_reserve(spx_ctx* ctx, size_t n_slots);
+/* Opt-in REFRESH TABLES ("finny tables": RefreshTable, src/eval/nnue/input.h:308-328; refreshPsqAccumulator,
+ * src/eval/nnue_state.cpp:458-524). A table has 32 entries - one per (king bucket, mirror half), getRefreshTableEntry
+ * (src/eval/nnue/features/psq.h:256-262) - x 2 colours; each cell holds an i16[1024] piece-square accumulator (FT bias
+ * included) and the 12 piece bitboards it was built from, ~134 KiB per table (4 096 tables ~560 MB, 65 536 ~9 GB).
+ * A perspective whose king changed bucket or mirror half is rebuilt by the pass behind the update kernel; with a table it is
+ * rebuilt from the table's cell instead: only the piece-square rows of the squares that differ from the cell's bitboards
+ * are applied, the cell is written back, and the board's threat / pawn-pair rows are added as before.
+ *   spx_acc_reserve_refresh_tables sizes the store (never shrinks; growing keeps the existing tables). Every context starts
+ *     with zero tables = the feature is off and every kernel runs exactly the code it runs without the feature. A new table
+ *     is RefreshTable::init's: the bias and empty bitboards. n_tables <= 2^24.
+ *   spx_acc_bind_refresh_tables binds arena slots[i] to tables[i] (SPX_NO_TABLE unbinds; every slot starts unbound). The
+ *     bindings are a static per-slot array the caller sets - as an engine gives each search thread (or game) its own table -
+ *     and spx_acc_reserve growth keeps them. Out-of-range slots or tables: SPX_ERR_INVALID_ARG. Needs the arena; synchronises.
+ * A record consults the table bound to its PARENT slot (eval-only children are covered); records whose parent is unbound
+ * behave exactly as without tables. Siblings of one batch that need the same cell: one of them uses it, the others are
+ * rebuilt from scratch. RESULTS NEVER DEPEND ON TABLE CONTENTS: any cell is exact for the bitboards it stores, so tables may
+ * be shared between games, stale, or primed by another game. Two batches that may run AT THE SAME TIME (different streams
+ * without ordering) must not use the same table; the *_async calls order themselves.
+ * Consulted by every batch that runs spx_update_kernel + its rebuild pass: spx_acc_update*, spx_acc_update_eval* (counted and
+ * async included) and self-play (SPX_SELFPLAY_REFRESH_TABLES). NOT consulted (they rebuild as before - not writing a cell is
+ * always correct): the single-launch chain kernel of batches <= option update_chain_max, spx_acc_update_observed*,
+ * spx_acc_update_chain_eval, the path mode of spx_acc_replay_tree, spx_acc_refresh* and include/spx_nnue.hpp. */
+#define SPX_NO_TABLE 0xFFFFFFFFu
+int spx_acc_reserve_refresh_tables(spx_ctx* ctx, size_t n_tables);
+int spx_acc_bind_refresh_tables(spx_ctx* ctx, const uint32_t* slots, const uint32_t* tables, size_t n);
 int spx_acc_refresh(spx_ctx* ctx, const spx_packed_pos* positions, const uint32_t* slots, size_t n);
 int spx_acc_update(spx_ctx* ctx, const uint32_t* parent_slots, const uint32_t* child_slots,
                    const spx_packed_pos* child_positions, size_t n);
@@ -478,10 +503,14 @@ typedef struct spx_selfplay_params {
     uint32_t host_threads;   /* host worker threads of the HOST move generation path; 0 = auto: min(16, usable CPUs = cgroup quota /
                               * LOCAL_WORLD_SIZE). The device-resident games need one host thread */
     uint32_t flags;          /* 0 = moves generated on the device; SPX_SELFPLAY_HOST_MOVEGEN = host chess core instead;
+                              * | SPX_SELFPLAY_REFRESH_TABLES: one refresh table per seat (device path only);
                               * | SPX_SELFPLAY_SEARCH_NODES(k): a live fixed-node search picks the moves (device path only) */
     uint64_t seed;
 } spx_selfplay_params;
-enum { SPX_SELFPLAY_HOST_MOVEGEN = 1 };
+enum { SPX_SELFPLAY_HOST_MOVEGEN = 1, SPX_SELFPLAY_REFRESH_TABLES = 2 };
+/* SPX_SELFPLAY_REFRESH_TABLES (device-resident driver, depth-1 and search): one refresh table per seat (spx_acc_reserve_refresh_tables;
+ * ~134 KiB each), every arena slot of the seat bound to it before any graph capture. Games are byte-identical with and without
+ * it. The host move generation path refuses the flag (SPX_ERR_INVALID_ARG). */
 /* Live fixed-node search in place of the depth-1 policy (datagen's Searcher::runDatagenSearch with its soft node limit,
  * search.cpp:212-239, datagen.cpp:78-80): every game runs its own iterative-deepening alpha-beta, ONE node expanded per game
  * and round, the node's children evaluated in the same batch as every other game's - k = nodes a search may expand before it

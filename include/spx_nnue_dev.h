@@ -57,6 +57,11 @@ int spx_random_successors(uint64_t seed, const spx_packed_pos* positions, size_t
 /* One random game as a viriformat stream (test / demo input; the scores are random). */
 int spx_viri_random_game(uint64_t seed, int plies, int dfrc, void* buf, size_t capacity, size_t* nbytes);
 
+/* Counters of the context's refresh tables (spx_acc_reserve_refresh_tables) since the last read: out[0] perspectives the rebuild
+ * passes rebuilt, out[1] how many of them a table served, out[2] piece-square rows the table path applied, out[3] piece-square
+ * rows from-scratch rebuilds of those served perspectives would have applied. Synchronises the device and clears them. */
+int spx_debug_refresh_table_stats(spx_ctx* ctx, uint64_t out[4]);
+
 /* perft of the host chess core (legal move generation check against published counts). */
 uint64_t spx_perft(const char* fen, int depth);
 

@@ -105,6 +105,9 @@ SYMBOLS = {
     "spx_profile_last_prepare_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     "spx_profile_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_size_t)]),
     "spx_acc_reserve": (ctypes.c_int, [_P, ctypes.c_size_t]),
+    "spx_acc_reserve_refresh_tables": (ctypes.c_int, [_P, ctypes.c_size_t]),
+    "spx_acc_bind_refresh_tables": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t]),
+    "spx_debug_refresh_table_stats": (ctypes.c_int, [_P, _P]),
     "spx_acc_refresh": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t]),
     "spx_acc_update": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_size_t]),
     "spx_acc_eval": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P]),

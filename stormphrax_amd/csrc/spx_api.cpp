@@ -173,6 +173,16 @@ struct spx_ctx {
     uint8_t* dArena = nullptr;
     uint8_t* dSlotRecords = nullptr;
     size_t nSlots = 0;
+    // opt-in refresh tables (spx_acc_reserve_refresh_tables): nTables x kRtCells cells (i16[1024] piece-square accumulator + 12
+    // bitboards + a claim word each), the slots' bindings [nSlots] (allocated by the first bind, grown with the arena) and the
+    // counters read by spx_debug_refresh_table_stats. nTables == 0 or no bindings: every kernel runs its table-less instantiation
+    size_t nTables = 0;
+    int16_t* dRtAcc = nullptr;
+    uint64_t* dRtBbs = nullptr;
+    uint32_t* dRtClaims = nullptr;
+    unsigned long long* dRtStats = nullptr;
+    uint32_t* dSlotTable = nullptr;
+    std::vector<uint32_t> slotTable;  // host copy of the bindings
     uint32_t *dSlotsA = nullptr, *dSlotsB = nullptr;  // staging for the host-buffer entry points [max_batch]
     uint8_t* dDeltas = nullptr;                        // [max_batch] spx_move_delta staging (allocated on first use)
     // spx_eval_full_device_async: two scratch sets ("lanes") with their own streams alternate, so that the sorts and
@@ -861,7 +871,8 @@ void spx_ctx_destroy(spx_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     void* ptrs[] = {ctx->dPsqW, ctx->dThrW, ctx->dFtBias, ctx->dL1W, ctx->dL1B, ctx->dL2W,  ctx->dL2B,
                     ctx->dL3W,  ctx->dL3B, ctx->dLut,    ctx->dDeltaTab, ctx->dOutlierTab, ctx->dPositions, ctx->dOut,
-                    ctx->dArena, ctx->dSlotRecords, ctx->dSlotsA, ctx->dSlotsB, ctx->dDeltas};
+                    ctx->dArena, ctx->dSlotRecords, ctx->dSlotsA, ctx->dSlotsB, ctx->dDeltas,
+                    ctx->dRtAcc, ctx->dRtBbs, ctx->dRtClaims, ctx->dRtStats, ctx->dSlotTable};
     for (void* p : ptrs) {
         if (p) (void)hipFree(p);
     }
@@ -1389,18 +1400,126 @@ int spx_acc_reserve(spx_ctx* ctx, size_t n_slots) {
         e = hipMemcpy(arena, ctx->dArena, ctx->nSlots * kAccSlotBytes, hipMemcpyDeviceToDevice);
         if (e == hipSuccess) e = hipMemcpy(records, ctx->dSlotRecords, ctx->nSlots * 32, hipMemcpyDeviceToDevice);
     }
+    // refresh-table bindings (once any exist): the new slots start unbound
+    uint32_t* slotTable = nullptr;
+    if (e == hipSuccess && ctx->dSlotTable) {
+        e = hipMalloc(reinterpret_cast<void**>(&slotTable), n_slots * 4);
+        if (e == hipSuccess) e = hipMemset(slotTable, 0xFF, n_slots * 4);
+        if (e == hipSuccess) e = hipMemcpy(slotTable, ctx->dSlotTable, ctx->nSlots * 4, hipMemcpyDeviceToDevice);
+    }
     if (e == hipSuccess) e = hipDeviceSynchronize();  // null-stream work vs. the non-blocking streams that use the arena next
     if (e != hipSuccess) {
         (void)hipFree(arena);
         (void)hipFree(records);
+        if (slotTable) (void)hipFree(slotTable);
         setError(std::string("spx_acc_reserve: ") + hipGetErrorString(e));
         return SPX_ERR_HIP;
+    }
+    if (slotTable) {
+        (void)hipFree(ctx->dSlotTable);
+        ctx->dSlotTable = slotTable;
+        ctx->slotTable.resize(n_slots, SPX_NO_TABLE);
     }
     if (ctx->dArena) (void)hipFree(ctx->dArena);
     if (ctx->dSlotRecords) (void)hipFree(ctx->dSlotRecords);
     ctx->dArena = arena;
     ctx->dSlotRecords = records;
     ctx->nSlots = n_slots;
+    return SPX_OK;
+}
+
+// ---- opt-in refresh tables (RefreshTable, src/eval/nnue/input.h:308-328; refreshPsqAccumulator, nnue_state.cpp:458-524) ----
+int spx_acc_reserve_refresh_tables(spx_ctx* ctx, size_t n_tables) {
+    if (!ctx || n_tables > (size_t(1) << 24)) {
+        setError("spx_acc_reserve_refresh_tables: invalid argument");
+        return SPX_ERR_INVALID_ARG;
+    }
+    if (n_tables <= ctx->nTables) return SPX_OK;
+    SPX_HIP(hipSetDevice(ctx->device));
+    SPX_HIP(hipDeviceSynchronize());
+    const size_t cells = n_tables * kRtCells, oldCells = ctx->nTables * kRtCells;
+    int16_t* acc = nullptr;
+    uint64_t* bbs = nullptr;
+    uint32_t* claims = nullptr;
+    unsigned long long* stats = ctx->dRtStats;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&acc), cells * kL1 * 2);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&bbs), cells * 12 * 8);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&claims), cells * 4);
+    if (e == hipSuccess && !stats) {
+        e = hipMalloc(reinterpret_cast<void**>(&stats), 4 * 8);
+        if (e == hipSuccess) e = hipMemset(stats, 0, 4 * 8);
+    }
+    // existing tables are kept; a new one is RefreshTable::init's: every cell = the FT bias, empty bitboards
+    if (e == hipSuccess) e = hipMemset(bbs, 0, cells * 12 * 8);
+    if (e == hipSuccess) e = hipMemset(claims, 0, cells * 4);
+    if (e == hipSuccess && oldCells) {
+        e = hipMemcpy(acc, ctx->dRtAcc, oldCells * kL1 * 2, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(bbs, ctx->dRtBbs, oldCells * 12 * 8, hipMemcpyDeviceToDevice);
+    }
+    if (e == hipSuccess) {  // the first new cell from the host, then doubling device copies
+        std::vector<int16_t> bias(kL1);
+        e = hipMemcpy(bias.data(), ctx->dFtBias, kL1 * 2, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(acc + oldCells * kL1, bias.data(), kL1 * 2, hipMemcpyHostToDevice);
+        for (size_t done = 1; e == hipSuccess && oldCells + done < cells; done *= 2) {
+            const size_t m = std::min(done, cells - oldCells - done);
+            e = hipMemcpy(acc + (oldCells + done) * kL1, acc + oldCells * kL1, m * kL1 * 2, hipMemcpyDeviceToDevice);
+        }
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        for (void* q : {static_cast<void*>(acc), static_cast<void*>(bbs), static_cast<void*>(claims)}) {
+            if (q) (void)hipFree(q);
+        }
+        if (stats != ctx->dRtStats) (void)hipFree(stats);
+        setError(std::string("spx_acc_reserve_refresh_tables: ") + hipGetErrorString(e));
+        return SPX_ERR_HIP;
+    }
+    for (void* q : {static_cast<void*>(ctx->dRtAcc), static_cast<void*>(ctx->dRtBbs), static_cast<void*>(ctx->dRtClaims)}) {
+        if (q) (void)hipFree(q);
+    }
+    ctx->dRtAcc = acc;
+    ctx->dRtBbs = bbs;
+    ctx->dRtClaims = claims;
+    ctx->dRtStats = stats;
+    ctx->nTables = n_tables;
+    return SPX_OK;
+}
+
+int spx_acc_bind_refresh_tables(spx_ctx* ctx, const uint32_t* slots, const uint32_t* tables, size_t n) {
+    if (!ctx || (n && (!slots || !tables)) || !ctx->dArena) {
+        setError("spx_acc_bind_refresh_tables: invalid argument (null pointer, or no arena: call spx_acc_reserve first)");
+        return SPX_ERR_INVALID_ARG;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (slots[i] >= ctx->nSlots || (tables[i] != SPX_NO_TABLE && tables[i] >= ctx->nTables)) {
+            setError("spx_acc_bind_refresh_tables: binding " + std::to_string(i) + " (slot " + std::to_string(slots[i]) +
+                     ", table " + std::to_string(tables[i]) + ") out of range");
+            return SPX_ERR_INVALID_ARG;
+        }
+    }
+    SPX_HIP(hipSetDevice(ctx->device));
+    SPX_HIP(hipDeviceSynchronize());  // (kernels in flight read the bindings)
+    if (!ctx->dSlotTable) {
+        SPX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->dSlotTable), ctx->nSlots * 4));
+        ctx->slotTable.assign(ctx->nSlots, SPX_NO_TABLE);
+    }
+    for (size_t i = 0; i < n; ++i) ctx->slotTable[slots[i]] = tables[i];
+    SPX_HIP(hipMemcpy(ctx->dSlotTable, ctx->slotTable.data(), ctx->nSlots * 4, hipMemcpyHostToDevice));
+    return SPX_OK;
+}
+
+int spx_debug_refresh_table_stats(spx_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) {
+        setError("spx_debug_refresh_table_stats: invalid argument");
+        return SPX_ERR_INVALID_ARG;
+    }
+    std::memset(out, 0, 4 * 8);
+    if (!ctx->dRtStats) return SPX_OK;
+    SPX_HIP(hipSetDevice(ctx->device));
+    SPX_HIP(hipDeviceSynchronize());
+    SPX_HIP(hipMemcpy(out, ctx->dRtStats, 4 * 8, hipMemcpyDeviceToHost));
+    SPX_HIP(hipMemset(ctx->dRtStats, 0, 4 * 8));
+    SPX_HIP(hipDeviceSynchronize());
     return SPX_OK;
 }
 
@@ -1498,8 +1617,18 @@ static int launchUpdateAndRefresh(const spx_ctx* ctx, ScratchSet& x, UpdateParam
         SPX_HIP(launchUpdateChain(cp, s));
         return SPX_OK;
     }
+    if (ctx->nTables && ctx->dSlotTable) {  // refresh tables: the deferred perspectives of bound parents claim their cells
+        up.rt.slotTable = ctx->dSlotTable;
+        up.rt.parentSlots = up.parentSlots;
+        up.rt.nTables = uint32_t(ctx->nTables);
+        up.rt.claims = ctx->dRtClaims;
+        up.rt.acc = ctx->dRtAcc;
+        up.rt.bbs = ctx->dRtBbs;
+        up.rt.stats = ctx->dRtStats;
+    }
     SPX_HIP(launchUpdate(up, updateGrid(ctx, split ? 2 * n : n), split, streamAcc, s));
     FtParams fp{};
+    fp.rt = up.rt;
     fp.positions = up.childPositions;
     fp.nPositions = uint32_t(n);
     fp.order = up.refreshList;

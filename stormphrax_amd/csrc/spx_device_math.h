@@ -167,6 +167,12 @@ SPX_HD int kingBucket(int kingSqRel) {  // kingSqRel: king square already rank-f
     return int(((i < 16 ? lo : hi) >> ((i & 15) * 4)) & 0xF);
 }
 
+// InputFeatureSet::getRefreshTableEntry (psq.h:256-262): the refresh-table entry of perspective c's king on kingSq = king
+// bucket x 2 + mirror half (files e-h), the same bucket and mirror that psqRow below maps the piece-square rows by
+SPX_HD uint32_t refreshTableEntry(int c, int kingSq) {
+    return uint32_t(kingBucket(c == 0 ? (kingSq ^ 56) : kingSq)) * 2u + ((kingSq & 7) >= 4 ? 1u : 0u);
+}
+
 // psq::featureIndex (psq.h:338-365): row of (piece, sq) for perspective c whose own king stands on kingSq.
 SPX_HD uint32_t psqRow(int c, int piece, int sq, int kingSq) {
     const uint32_t type = uint32_t(piece >> 1);

@@ -274,7 +274,8 @@ __device__ __forceinline__ uint64_t laneTargets(const LaneBoard& b, uint32_t lan
 // kNear (full-refresh kernel of a net that has near-compact rows): such rows take the 1 KiB path too; the remainders of
 // their <= kOutlierCap wide weights (FtTables::outlierTab) are summed per column into `nearAcc` (this wave's 1 024 i32 in
 // LDS; lane = the row's square, one LDS atomic per remainder) and folded in after the gather. Returns whether any was.
-template <bool kNear = false>
+// kPsq = false (the refresh-table path of the rebuild pass): threat and pawn-pair rows only, nPsq = 0.
+template <bool kNear = false, bool kPsq = true>
 __device__ __forceinline__ bool buildFullLists(const LaneBoard& b, int c, uint32_t lane, const uint32_t* lut,
                                                uint32_t* psqList, uint32_t* thrList, uint32_t& nPsq, uint32_t& nThr,
                                                const uint64_t* pseudoTab = nullptr,
@@ -292,8 +293,10 @@ __device__ __forceinline__ bool buildFullLists(const LaneBoard& b, int c, uint32
 
     // piece-square rows: one per occupied square (resetPsqAccumulator, nnue_state.cpp:440-449). Rows whose weights all
     // fit i8 have a 1 KiB copy in the u8 table: those go to the head of the u8 list, the rest to the i16 list.
-    uint32_t nCompact;
-    {
+    uint32_t nCompact = 0;
+    if constexpr (!kPsq) {
+        nPsq = 0;
+    } else {
         uint32_t row = 0;
         bool compact = false, near = false;
         if (occupied) {

@@ -16,6 +16,21 @@ constexpr int kHistWords = 1024;  // one sort-histogram buffer (counts + cursors
 
 constexpr size_t kAccSlotBytes = 2 * 1024 * 2;  // one arena slot: 2 perspectives x i16[1024] (psq + threat combined)
 
+// Opt-in refresh tables ("finny tables", src/eval/nnue/input.h:308-328; spx_acc_reserve_refresh_tables): per table 32 entries
+// (king bucket x mirror half, psq.h:256-262) x 2 colours; a cell holds an i16[1024] piece-square-only accumulator (FT bias
+// included) and the 12 piece bitboards it was built from. All null = off: the kernels run their table-less instantiations.
+constexpr uint32_t kNoTable = 0xFFFFFFFFu;
+constexpr uint32_t kRtCells = 64;  // cells per table: entry * 2 + colour
+struct RefreshTableArgs {
+    const uint32_t* slotTable;    // [nSlots] table bound to each arena slot, or kNoTable
+    const uint32_t* parentSlots;  // rebuild pass: each record's parent slot (the table a record consults is its parent's)
+    uint32_t nTables;
+    uint32_t* claims;             // [nTables * kRtCells] 2 * record + colour + 1 of the perspective that may use the cell; 0 = free
+    int16_t* acc;                 // [nTables * kRtCells][1024]
+    uint64_t* bbs;                // [nTables * kRtCells][12] piece bitboards (index = piece = type << 1 | colour)
+    unsigned long long* stats;    // [4] rebuilt, served by a table, psq rows applied by the table path, psq rows of scratch rebuilds
+};
+
 // device-resident network tables shared by the feature-transformer and update kernels
 struct FtTables {
     const int16_t* psqW;     // [11264][1024] i16, logical column order
@@ -37,6 +52,7 @@ struct FtParams {
     const uint32_t* nPerspPtr;  // optional: number of entries of `order` lives on the device (deferred refresh list)
     uint32_t* clearWord;        // optional: a device word this launch zeroes (the refresh counter of the NEXT update)
     uint8_t* slotRecords;    //         ... and the per-slot record store [nSlots][32]
+    RefreshTableArgs rt;     // rebuild pass of an update on a context with refresh tables (else all null)
 };
 
 struct UpdateParams {
@@ -55,6 +71,7 @@ struct UpdateParams {
     uint8_t* stagedRecords;        // ... and [nRecords][32] their records (input of the MLP's bucket sort)
     uint32_t* refreshList;         // spx_update_kernel: ids (2 * record + colour) of the perspectives to rebuild ...
     uint32_t* refreshCount;        // ... and their number (zero on entry); the FT kernel launched next consumes both
+    RefreshTableArgs rt;           // spx_update_kernel on a context with refresh tables: deferred perspectives claim their cell
 };
 
 struct ChainParams {               // spx_update_chain_kernel: whole pending PATHS (NnueState::ensureUpToDate) in one launch

@@ -44,8 +44,15 @@ namespace spx {
 // (Round 4 also ran this kernel's gather on the matrix pipe - gatherFullMfma, SPX_FT_MFMA_GATHER=1: half the VALU instructions, the
 // same time, 88 MB of extra tables; retired in round 5 to experiments/r04_ft_kernel_gather_on_the_matrix_pipe.hip.txt. The
 // column-sliced pipeline, spx_ftx.hip, is where that idea pays.)
-template <bool kNear>
-__global__ __launch_bounds__(64 * kWavesPerBlock, SPX_FT_WAVES_PER_SIMD) void spx_ft_kernel(FtParams p) {
+// kTable (rebuild pass on a context with refresh tables, p.rt): a perspective that holds its cell's claim is rebuilt from the
+// cell (tableRefresh, below); every other one exactly as without tables. kTable = false is the table-less code.
+namespace {
+__device__ __forceinline__ bool tableRefresh(const FtParams& p, const LaneBoard& b, uint32_t q, uint32_t lane, const uint32_t* sLut,
+                                             const uint64_t* sPseudo, uint32_t* thrList, uint32_t* psqList, uint32_t (&acc)[8]);
+}
+// (kTable at 5 waves/SIMD spills 76 B: 4)
+template <bool kNear, bool kTable>
+__global__ __launch_bounds__(64 * kWavesPerBlock, kTable ? 4 : SPX_FT_WAVES_PER_SIMD) void spx_ft_kernel(FtParams p) {
     __shared__ uint32_t sLut[kLutWords];
     __shared__ __align__(16) int32_t sNear[kNear ? kWavesPerBlock : 1][kNear ? int(kL1) : 4];  // per-column remainder sums
     __shared__ uint32_t sThr[kWavesPerBlock][kU8Cap];  // byte offsets into the threat table
@@ -55,6 +62,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, SPX_FT_WAVES_PER_SIMD) void sp
     if (p.clearWord && blockIdx.x == 0 && threadIdx.x == 0) *p.clearWord = 0;
     // nPerspPtr: the list in `order` was produced on the device (deferred refreshes of the update kernel) and so was its length
     const uint32_t nPersp = p.nPerspPtr ? min(*p.nPerspPtr, p.nPositions * 2) : p.nPositions * 2;
+    if constexpr (kTable) {  // perspectives rebuilt: one atomic per launch
+        if (blockIdx.x == 0 && threadIdx.x == 0 && nPersp) atomicAdd(p.rt.stats, static_cast<unsigned long long>(nPersp));
+    }
     // XCD-aware traversal: workgroup b runs on XCD b % 8 (observed dispatch order; affects speed only). The (king-bucket
     // sorted) perspective order is dealt to the XCDs in chunks of SPX_FT_CHUNK perspectives, round robin: all eight walk
     // the order side by side, so at any moment each private 4 MiB L2 holds the 0.7-1.4 MiB piece-square slab of the SAME
@@ -93,11 +103,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, SPX_FT_WAVES_PER_SIMD) void sp
 
         const uint8_t* rec = reinterpret_cast<const uint8_t*>(p.positions) + size_t(posIdx) * 32;
         const LaneBoard board = decodeBoard(rec, lane);
-        uint32_t nPsq, nThr;
-        const bool hasNear = buildFullLists<kNear>(board, c, lane, sLut, sPsq[wave], sThr[wave], nPsq, nThr, sPseudo,
-                                                          p.t.outlierTab, sNear[kNear ? wave : 0]);
         uint32_t acc[8];
-        gatherFull(p.t, lane, sPsq[wave], nPsq, sThr[wave], nThr, acc, (kNear && hasNear) ? sNear[kNear ? wave : 0] : nullptr);
+        bool served = false;
+        if constexpr (kTable) served = tableRefresh(p, board, q, lane, sLut, sPseudo, sThr[wave], sPsq[wave], acc);
+        if (!served) {
+            uint32_t nPsq, nThr;
+            const bool hasNear = buildFullLists<kNear>(board, c, lane, sLut, sPsq[wave], sThr[wave], nPsq, nThr, sPseudo,
+                                                       p.t.outlierTab, sNear[kNear ? wave : 0]);
+            gatherFull(p.t, lane, sPsq[wave], nPsq, sThr[wave], nThr, acc, (kNear && hasNear) ? sNear[kNear ? wave : 0] : nullptr);
+        }
 
         if (p.accOut) {
             const uint32_t slot = __builtin_amdgcn_readfirstlane(p.slots[posIdx]);
@@ -365,6 +379,143 @@ __device__ __forceinline__ uint32_t emitPawnPairDelta(uint32_t* list, uint32_t n
     return n;
 }
 
+
+// ---- refresh tables (opt-in; RefreshTableArgs in spx_kernels.h, spx_acc_reserve_refresh_tables in include/spx_nnue.h) ----
+// One writer per cell and launch: every deferred perspective whose parent slot is bound to a table takes an agent-scope
+// atomicMax of (its id + 1) on its cell's claim word in the update kernel; in the rebuild pass launched behind it (the kernel
+// boundary orders the claims before their use) only the perspective whose id the word holds reads the cell, applies the
+// difference and writes it back, and clears the word for the next update. Its siblings of the same cell rebuild from scratch.
+__device__ __forceinline__ uint32_t rtCell(uint32_t table, int c, int kingSq) {
+    return table * kRtCells + refreshTableEntry(c, kingSq) * 2u + uint32_t(c);
+}
+
+// (the deferred perspectives [cFirst, cLast) of record `it` with refresh[c] set)
+__device__ __forceinline__ void claimRefreshCells(const RefreshTableArgs& rt, uint32_t parentSlot, const uint8_t* childRec, int cFirst,
+                                                  int cLast, const bool (&refresh)[2], uint32_t it, uint32_t lane) {
+    const uint32_t table = __builtin_amdgcn_readfirstlane(rt.slotTable[parentSlot]);
+    if (table >= rt.nTables) return;  // (kNoTable: unbound)
+    const LaneBoard b = decodeBoard(childRec, lane);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        if (c < cFirst || c >= cLast || !refresh[c]) continue;
+        const uint64_t own = b.kingsBb & (c ? b.whiteBb : ~b.whiteBb);
+        if (lane == 0) {
+            __hip_atomic_fetch_max(rt.claims + rtCell(table, c, own ? ctz64(own) : 0), 2u * it + uint32_t(c) + 1u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// one piece-square row per `active` lane (<= 32 of them): compact rows into u8List, the others (near-compact rows included:
+// the i16 table holds them exactly) into wideList. Returns the number of compact rows; nWide by reference.
+__device__ __forceinline__ uint32_t emitPsqRows32(bool active, uint32_t row, const uint32_t* lut, uint32_t* wideList,
+                                                  uint32_t* u8List, uint32_t& nWide) {
+    const bool compact = active && ((lut[kLutCompactBase + (row >> 5)] >> (row & 31)) & 1u);
+    const uint64_t compactMask = __ballot(compact), wideMask = __ballot(active && !compact);
+    const uint32_t slot = prefixCount(compact ? compactMask : wideMask);
+    if (active) {
+        if (compact) {
+            u8List[slot] = (kThreatRows + row) * kL1;
+        } else {
+            wideList[slot] = row * (kL1 * 2);
+        }
+    }
+    nWide = uint32_t(popc64(wideMask));
+    return uint32_t(popc64(compactMask));
+}
+
+// refreshPsqAccumulator (nnue_state.cpp:458-524) for perspective q = 2 * record + c of the rebuild pass: when q holds its
+// cell's claim, the cell's piece-square accumulator is brought to this board by the rows of the squares whose piece differs
+// from the cell's bitboards, stored back with the new bitboards, and acc = cell + the board's threat / pawn-pair rows - bit
+// for bit the from-scratch sum (everything wraps mod 2^16). Returns false (acc untouched) when the pass rebuilds q as usual.
+__device__ __forceinline__ bool tableRefresh(const FtParams& p, const LaneBoard& b, uint32_t q, uint32_t lane, const uint32_t* sLut,
+                                             const uint64_t* sPseudo, uint32_t* thrList, uint32_t* psqList, uint32_t (&acc)[8]) {
+    const int c = int(q & 1);
+    const uint32_t parent = __builtin_amdgcn_readfirstlane(p.rt.parentSlots[q >> 1]);
+    const uint32_t table = __builtin_amdgcn_readfirstlane(p.rt.slotTable[parent]);
+    if (table >= p.rt.nTables) return false;
+    const uint64_t own = b.kingsBb & (c ? b.whiteBb : ~b.whiteBb);
+    const int kingSq = own ? ctz64(own) : 0;
+    const uint32_t cell = rtCell(table, c, kingSq);
+    uint32_t* claim = p.rt.claims + cell;
+    const uint32_t holder = __builtin_amdgcn_readfirstlane(__hip_atomic_load(claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    if (holder != q + 1u) return false;
+    // the cell is this wave's for the rest of the launch: release the word for the next update (the other perspectives of the
+    // cell compare it with their own ids, which it never equals)
+    if (lane == 0) __hip_atomic_store(claim, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+
+    // the cell's bitboards: lane k < 12 holds piece k's; old = the piece the cell has on this lane's square
+    uint64_t* bbCell = p.rt.bbs + size_t(cell) * 12;
+    const uint64_t mine = lane < 12 ? bbCell[lane] : 0;
+    int old = kNoPiece;
+    uint64_t fresh = 0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const uint64_t o = (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mine >> 32)), k))) << 32) |
+                           uint32_t(__builtin_amdgcn_readlane(int(uint32_t(mine)), k));
+        if ((o >> lane) & 1) old = k;
+        const uint64_t now = __ballot(b.piece == k);
+        if (lane == uint32_t(k)) fresh = now;
+    }
+    const bool subLane = old != b.piece && old != kNoPiece, addLane = old != b.piece && b.piece != kNoPiece;
+    if (popc64(__ballot(subLane)) > kPsqCap || popc64(__ballot(addLane)) > kPsqCap) return false;  // (malformed records only)
+
+    // piece-square rows that differ (<= 32 + 32): u8 sub / add, wide sub / add, in the wave's threat list space
+    uint32_t* u8Sub = thrList;
+    uint32_t* u8Add = thrList + 32;
+    uint32_t* wideSub = thrList + 64;
+    uint32_t* wideAdd = thrList + 96;
+    uint32_t nWideSub, nWideAdd;
+    const uint32_t nSub = emitPsqRows32(subLane, subLane ? psqRow(c, old, int(lane), kingSq) : 0u, sLut, wideSub, u8Sub, nWideSub);
+    const uint32_t nAdd = emitPsqRows32(addLane, addLane ? psqRow(c, b.piece, int(lane), kingSq) : 0u, sLut, wideAdd, u8Add, nWideAdd);
+    __builtin_amdgcn_wave_barrier();
+    uint8_t* entry = reinterpret_cast<uint8_t*>(p.rt.acc + size_t(cell) * kL1) + 16 * lane;
+    uint32_t psq[8];
+    {
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(entry), hi = *reinterpret_cast<const u32x4*>(entry + 1024);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            psq[r] = lo[r];
+            psq[4 + r] = hi[r];
+        }
+    }
+    applyWidePsqDelta(p.t, lane, wideSub, nWideSub, wideAdd, nWideAdd, psq);
+    applyU8Delta(p.t, lane, u8Add, nAdd, u8Sub, nSub, psq);
+    {
+        u32x4 lo, hi;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            lo[r] = psq[r];
+            hi[r] = psq[4 + r];
+        }
+        *reinterpret_cast<u32x4*>(entry) = lo;
+        *reinterpret_cast<u32x4*>(entry + 1024) = hi;
+    }
+    if (lane < 12) bbCell[lane] = fresh;
+    const uint32_t psqOcc = uint32_t(popc64(b.occ));
+    if (lane < 3) {  // served, psq rows applied, psq rows a from-scratch rebuild fetches: one atomic instruction per serving wave
+        const uint32_t applied = nSub + nAdd + nWideSub + nWideAdd;
+        atomicAdd(p.rt.stats + 1 + lane,
+                  static_cast<unsigned long long>(lane == 0 ? 1u : (lane == 1 ? applied : psqOcc)));
+    }
+    __builtin_amdgcn_wave_barrier();  // the piece-square lists are dead before the threat list overwrites them
+
+    // + the board's threat and pawn-pair rows (gatherFull adds the bias once more: taken off again). The cell is read back
+    // rather than held through the gather (8 VGPRs there spill): this wave's own stores, in order
+    uint32_t nPsq, nThr;
+    buildFullLists<false, false>(b, c, lane, sLut, psqList, thrList, nPsq, nThr, sPseudo);
+    gatherFull(p.t, lane, psqList, 0, thrList, nThr, acc);
+    const u32x4 b0 = *reinterpret_cast<const u32x4*>(p.t.ftBias + 8 * lane);
+    const u32x4 b1 = *reinterpret_cast<const u32x4*>(p.t.ftBias + 512 + 8 * lane);
+    const u32x4 e0 = *reinterpret_cast<const u32x4*>(entry), e1 = *reinterpret_cast<const u32x4*>(entry + 1024);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        acc[r] = pkAdd16(pkSub16(acc[r], b0[r]), e0[r]);
+        acc[4 + r] = pkAdd16(pkSub16(acc[4 + r], b1[r]), e1[r]);
+    }
+    return true;
+}
+
 }  // namespace
 
 #ifndef SPX_UPDATE_WAVES
@@ -485,9 +636,12 @@ __device__ __forceinline__ int deriveDeltaLists(const uint8_t* parentRec, const 
 // Perspectives that must be REBUILT (king changed bucket / mirror half, boards more than one move apart) are not
 // handled here: their ids (2 * record + colour) are appended to p.refreshList and the feature-transformer kernel,
 // launched right behind this one on the same stream, rebuilds exactly those (3-4 % of the perspectives in play).
-template <bool kSplit, bool kStream>
+// kTable (a context with refresh tables, p.rt): a deferred perspective whose parent slot is bound to a table also claims its
+// cell (claimRefreshCell) for the rebuild pass; kTable = false is the table-less code.
+template <bool kSplit, bool kStream, bool kTable>
 // (kSplit = small batches, bound by one record's latency: 4 waves/SIMD leave it the registers it spilled at 5)
-__global__ __launch_bounds__(64 * kWavesPerBlock, kSplit ? (SPX_UPDATE_WAVES > 4 ? 4 : SPX_UPDATE_WAVES) : SPX_UPDATE_WAVES) void spx_update_kernel(UpdateParams p) {
+// (kTable: the unsplit kernel at 5 waves/SIMD spills 20 B - 4)
+__global__ __launch_bounds__(64 * kWavesPerBlock, (kSplit || kTable) ? (SPX_UPDATE_WAVES > 4 ? 4 : SPX_UPDATE_WAVES) : SPX_UPDATE_WAVES) void spx_update_kernel(UpdateParams p) {
     __shared__ uint32_t sLut[kLutWords];
     __shared__ uint64_t sTab[kDeltaTabWords];                  // ray / knight masks + pseudo-attack sets (11 KiB)
     __shared__ uint32_t sAdd[kWavesPerBlock][2][kDeltaCap];    // per perspective: u8 rows to add ...
@@ -547,6 +701,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kSplit ? (SPX_UPDATE_WAVES > 4
                 const uint32_t half = (c == childStm) ? 0u : 1u;
                 *reinterpret_cast<u32x2*>(p.ftOut + size_t(it) * kL1 + half * kPairs + 8 * lane) = activate(acc);
             }
+        }
+        if constexpr (kTable) {
+            if (refresh[0] || refresh[1]) claimRefreshCells(p.rt, parentSlot, childRec, cFirst, cLast, refresh, it, lane);
         }
         __builtin_amdgcn_wave_barrier();  // this record's lists are dead before the next record's are written
         if (lane < 8 && cFirst == 0) {
@@ -1297,10 +1454,16 @@ hipError_t launchFtTeam(const FtParams& p, uint32_t gridBlocks, hipStream_t stre
 
 hipError_t launchFt(const FtParams& p, uint32_t gridBlocks, hipStream_t stream) {
     const dim3 grid(gridBlocks), block(64 * kWavesPerBlock);
-    if (p.t.outlierTab) {
-        hipLaunchKernelGGL((spx_ft_kernel<true>), grid, block, 0, stream, p);
+    if (p.rt.claims) {  // the rebuild pass of an update on a context with refresh tables
+        if (p.t.outlierTab) {
+            hipLaunchKernelGGL((spx_ft_kernel<true, true>), grid, block, 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((spx_ft_kernel<false, true>), grid, block, 0, stream, p);
+        }
+    } else if (p.t.outlierTab) {
+        hipLaunchKernelGGL((spx_ft_kernel<true, false>), grid, block, 0, stream, p);
     } else {
-        hipLaunchKernelGGL((spx_ft_kernel<false>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((spx_ft_kernel<false, false>), grid, block, 0, stream, p);
     }
     return hipGetLastError();
 }
@@ -1308,14 +1471,24 @@ hipError_t launchFt(const FtParams& p, uint32_t gridBlocks, hipStream_t stream) 
 hipError_t launchUpdate(const UpdateParams& p, uint32_t gridBlocks, bool splitPerspectives, bool streamAccumulators,
                         hipStream_t stream) {
     const dim3 grid(gridBlocks), block(64 * kWavesPerBlock);
-    if (splitPerspectives && streamAccumulators) {
-        hipLaunchKernelGGL((spx_update_kernel<true, true>), grid, block, 0, stream, p);
+    if (p.rt.claims) {  // a context with refresh tables
+        if (splitPerspectives && streamAccumulators) {
+            hipLaunchKernelGGL((spx_update_kernel<true, true, true>), grid, block, 0, stream, p);
+        } else if (splitPerspectives) {
+            hipLaunchKernelGGL((spx_update_kernel<true, false, true>), grid, block, 0, stream, p);
+        } else if (streamAccumulators) {
+            hipLaunchKernelGGL((spx_update_kernel<false, true, true>), grid, block, 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((spx_update_kernel<false, false, true>), grid, block, 0, stream, p);
+        }
+    } else if (splitPerspectives && streamAccumulators) {
+        hipLaunchKernelGGL((spx_update_kernel<true, true, false>), grid, block, 0, stream, p);
     } else if (splitPerspectives) {
-        hipLaunchKernelGGL((spx_update_kernel<true, false>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((spx_update_kernel<true, false, false>), grid, block, 0, stream, p);
     } else if (streamAccumulators) {
-        hipLaunchKernelGGL((spx_update_kernel<false, true>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((spx_update_kernel<false, true, false>), grid, block, 0, stream, p);
     } else {
-        hipLaunchKernelGGL((spx_update_kernel<false, false>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((spx_update_kernel<false, false, false>), grid, block, 0, stream, p);
     }
     return hipGetLastError();
 }

@@ -860,6 +860,24 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     if (rc != SPX_OK) return rc;
     SPX_SP_HIP(hipSetDevice(ctxDevice(ctx)));
     SPX_SP_HIP(hipMemset(ctxSlotRecords(ctx) + size_t(G) * 2 * 32, 0, 32));  // the null slot holds the empty board
+    if (p->flags & SPX_SELFPLAY_REFRESH_TABLES) {
+        // one refresh table per seat, every slot of the seat bound to it (the null slot stays unbound), before any capture:
+        // the seat's current / next slots s, G + s and its search levels 2 G + 1 + (L - 1) G + s
+        rc = spx_acc_reserve_refresh_tables(ctx, G);
+        if (rc != SPX_OK) return rc;
+        const size_t perSeatSlots = 2 + (search ? kSearchLevels - 1 : 0);
+        std::vector<uint32_t> bindSlots, bindTables;
+        bindSlots.reserve(size_t(G) * perSeatSlots);
+        bindTables.reserve(size_t(G) * perSeatSlots);
+        for (uint32_t seat = 0; seat < G; ++seat) {
+            for (size_t k = 0; k < perSeatSlots; ++k) {
+                bindSlots.push_back(k < 2 ? uint32_t(k) * G + seat : 2 * G + 1 + uint32_t(k - 2) * G + seat);
+                bindTables.push_back(seat);
+            }
+        }
+        rc = spx_acc_bind_refresh_tables(ctx, bindSlots.data(), bindTables.data(), bindSlots.size());
+        if (rc != SPX_OK) return rc;
+    }
     FILE* out = nullptr;
     if (out_path && out_path[0]) {
         out = std::fopen(out_path, "wb");
@@ -1291,8 +1309,9 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
 extern "C" int spx_selfplay_run(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_path,
                                 spx_selfplay_stats* stats) {
     if (!ctx || !p || !stats || p->n_games == 0 || p->target_games == 0 ||
-        (p->flags & 0xFFu & ~uint32_t(SPX_SELFPLAY_HOST_MOVEGEN)) ||
-        ((p->flags & SPX_SELFPLAY_HOST_MOVEGEN) && (p->flags >> 8))) {  // the search lives in the device-resident driver
+        (p->flags & 0xFFu & ~uint32_t(SPX_SELFPLAY_HOST_MOVEGEN | SPX_SELFPLAY_REFRESH_TABLES)) ||
+        ((p->flags & SPX_SELFPLAY_HOST_MOVEGEN) && (p->flags >> 8)) ||  // the search lives in the device-resident driver
+        ((p->flags & SPX_SELFPLAY_HOST_MOVEGEN) && (p->flags & SPX_SELFPLAY_REFRESH_TABLES))) {  // ... and so do the tables
         setError("spx_selfplay_run: invalid argument");
         return SPX_ERR_INVALID_ARG;
     }

@@ -28,6 +28,8 @@ assert PACKED_DTYPE.itemsize == 32
 
 PRESETS = {"tame": 0, "wild": 1, "extreme": 2, "realistic": 3}
 DEFAULT_SEED = 20260927
+NO_TABLE = 0xFFFFFFFF          # SPX_NO_TABLE: an unbound arena slot (spx_acc_bind_refresh_tables)
+SELFPLAY_REFRESH_TABLES = 2    # SPX_SELFPLAY_REFRESH_TABLES
 
 
 def synthetic_net_bytes(preset="tame", seed=DEFAULT_SEED):
@@ -287,6 +289,25 @@ class NnueState:
     def reserve_slots(self, n_slots):
         check(_lib.load().spx_acc_reserve(self._h, n_slots))
 
+    def reserve_refresh_tables(self, n_tables):
+        """spx_acc_reserve_refresh_tables: at least n_tables refresh tables (~134 KiB each; never shrinks). Results never depend
+        on their contents."""
+        check(_lib.load().spx_acc_reserve_refresh_tables(self._h, n_tables))
+
+    def bind_refresh_tables(self, slots, tables):
+        """spx_acc_bind_refresh_tables: arena slot slots[i] -> refresh table tables[i] (NO_TABLE unbinds)."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        tables = np.ascontiguousarray(tables, dtype=np.uint32)
+        assert slots.shape == tables.shape
+        check(_lib.load().spx_acc_bind_refresh_tables(self._h, slots.ctypes.data, tables.ctypes.data, slots.shape[0]))
+
+    def refresh_table_stats(self):
+        """spx_debug_refresh_table_stats (reads and clears): dict of perspectives rebuilt, served by a table, piece-square rows
+        the table path applied, piece-square rows from-scratch rebuilds of the served ones would have applied."""
+        out = np.zeros(4, dtype=np.uint64)
+        check(_lib.load().spx_debug_refresh_table_stats(self._h, out.ctypes.data))
+        return {"rebuilt": int(out[0]), "served": int(out[1]), "rows_applied": int(out[2]), "scratch_rows": int(out[3])}
+
     def reset(self, positions, slots):
         """NnueState::reset for each (position, slot): full refresh into the arena."""
         pos = np.ascontiguousarray(positions, dtype=PACKED_DTYPE)
@@ -343,13 +364,15 @@ class NnueState:
         return out
 
     def selfplay(self, n_games, target_games, out_path=None, max_plies=300, dfrc=False, temperature_cp=30, seed=1,
-                 host_threads=0, host_movegen=False, search_nodes=0):
+                 host_threads=0, host_movegen=False, search_nodes=0, refresh_tables=False):
         """Batched self-play (config 4 shape); returns the stats dict. See spx_selfplay_run.
         host_movegen=True generates moves with the host chess core instead of the device kernel.
+        refresh_tables=True: one refresh table per seat (SPX_SELFPLAY_REFRESH_TABLES; device path only, same games).
         search_nodes=k: a live fixed-node search of k expanded nodes picks every move (SPX_SELFPLAY_SEARCH_NODES; 0 = the
         depth-1 policy; k = 1 plays the same games through the search driver); stats["steps"] then counts expanded nodes."""
         params = _lib.SelfplayParams(n_games, target_games, max_plies, 0, int(dfrc), temperature_cp, host_threads,
-                                     (1 if host_movegen else 0) | (int(search_nodes) << 8), seed)
+                                     (1 if host_movegen else 0) | (SELFPLAY_REFRESH_TABLES if refresh_tables else 0)
+                                     | (int(search_nodes) << 8), seed)
         stats = _lib.SelfplayStats()
         check(_lib.load().spx_selfplay_run(self._h, ctypes.byref(params), out_path.encode() if out_path else None,
                                            ctypes.byref(stats)))
@@ -420,11 +443,11 @@ class DeviceGroup:
         return out
 
     def selfplay(self, n_games, target_games, out_path=None, max_plies=300, dfrc=False, temperature_cp=30, seed=1,
-                 search_nodes=0):
+                 search_nodes=0, refresh_tables=False):
         """spx_group_selfplay_run: the games dealt to the members, one host thread and one device each; output files
-        <out_path>.<member>.vf; summed stats."""
+        <out_path>.<member>.vf; summed stats. refresh_tables: every member its own tables (SPX_SELFPLAY_REFRESH_TABLES)."""
         params = _lib.SelfplayParams(n_games, target_games, max_plies, 0, int(dfrc), temperature_cp, 0,
-                                     int(search_nodes) << 8, seed)
+                                     (SELFPLAY_REFRESH_TABLES if refresh_tables else 0) | (int(search_nodes) << 8), seed)
         stats = _lib.SelfplayStats()
         check(_lib.load().spx_group_selfplay_run(self._h, ctypes.byref(params), out_path.encode() if out_path else None,
                                                  ctypes.byref(stats)))
