@@ -466,6 +466,21 @@ int spx_movegen(spx_ctx* ctx, const spx_packed_pos* positions, size_t n, const u
 int spx_movegen_device(spx_ctx* ctx, const void* d_positions, size_t n, const void* d_parent_values, void* d_children,
                        void* d_moves, void* d_parents, void* d_first, void* d_count, void* d_in_check, size_t capacity,
                        void* d_total, void* stream);
+/* The same with a MODE per position (one byte each; host / device array, NULL = all zero = the calls above):
+ *   0  every legal move;
+ *   1  the QUIESCENCE SET: every legal move when the side to move is in check, else the noisy legal moves
+ *      (Position::isNoisy, src/position.cpp:683-689: not castling, and en passant, a promotion to a queen or an occupied
+ *      target square - so a quiet promotion yields its queen alone, a capturing one all four pieces). count[i] = the
+ *      number of candidates, in_check[i] as above; the candidates keep the relative order of the full generation.
+ *   other values are reserved for later modes; today they behave as 0.
+ * What a host that batches its own quiescence search asks for (and what the self-play driver's quiescence nodes use):
+ * the move generation and the evaluation of a quiescence node cost its ~15 % noisy moves instead of all ~35. */
+int spx_movegen_modes(spx_ctx* ctx, const spx_packed_pos* positions, const uint8_t* modes, size_t n,
+                      const uint32_t* parent_values, spx_packed_pos* children, uint16_t* moves, uint32_t* parents,
+                      uint32_t* first, uint32_t* count, uint8_t* in_check, size_t capacity, size_t* total);
+int spx_movegen_modes_device(spx_ctx* ctx, const void* d_positions, const void* d_modes, size_t n, const void* d_parent_values,
+                             void* d_children, void* d_moves, void* d_parents, void* d_first, void* d_count, void* d_in_check,
+                             size_t capacity, void* d_total, void* stream);
 /* Host chess core, one position: legal moves (<= 256) in viriformat encoding and, if `children` is not NULL, the
  * records after them; *in_check = side to move is in check. The parity reference of spx_movegen. */
 int spx_pos_legal_moves(const spx_packed_pos* pos, uint16_t* moves, spx_packed_pos* children, int* n, int* in_check);
@@ -490,7 +505,8 @@ int spx_pos_legal_moves(const spx_packed_pos* pos, uint16_t* moves, spx_packed_p
  * launches, option selfplay_graph_plies = plies per graph), and the host reads ~100
  * bytes of counters plus the finished games per ply. SPX_SELFPLAY_HOST_MOVEGEN selects the host chess core for moves, openings and bookkeeping (the
  * same rules; the validation path). Needs a context whose max_batch holds a ply's children of half the seats (48 * n_games
- * is always enough); reserves 2 * n_games + 1 arena slots (129 * n_games with host move generation, 9 * n_games + 1 with a search).
+ * is always enough); reserves 2 * n_games + 1 arena slots (129 * n_games with host move generation, (9 + Q) * n_games + 1 with a search
+ * of Q quiescence plies, Q = 0 without them).
  * Multi-GPU: games are independent - run one process per GPU with its own seed / slice of games.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct spx_selfplay_params {
@@ -504,7 +520,8 @@ typedef struct spx_selfplay_params {
                               * LOCAL_WORLD_SIZE). The device-resident games need one host thread */
     uint32_t flags;          /* 0 = moves generated on the device; SPX_SELFPLAY_HOST_MOVEGEN = host chess core instead;
                               * | SPX_SELFPLAY_REFRESH_TABLES: one refresh table per seat (device path only);
-                              * | SPX_SELFPLAY_SEARCH_NODES(k): a live fixed-node search picks the moves (device path only) */
+                              * | SPX_SELFPLAY_SEARCH_NODES(k): a live fixed-node search picks the moves (device path only);
+                              * | SPX_SELFPLAY_QUIESCE_PLIES(q): ... whose horizon nodes are quiescence nodes (k >= 2) */
     uint64_t seed;
 } spx_selfplay_params;
 enum { SPX_SELFPLAY_HOST_MOVEGEN = 1, SPX_SELFPLAY_REFRESH_TABLES = 2 };
@@ -519,6 +536,23 @@ enum { SPX_SELFPLAY_HOST_MOVEGEN = 1, SPX_SELFPLAY_REFRESH_TABLES = 2 };
  * SearchStepParams in csrc/spx_kernels.h and restated in tests/_search_rules.py. 7 more arena slots per game;
  * stats.evals = leaves evaluated, stats.steps = nodes expanded. */
 #define SPX_SELFPLAY_SEARCH_NODES(k) ((uint32_t)(k) << 8)
+/* Quiescence search at the horizon of the live search (the role of qsearch, search.cpp:1451-1640), q = the plies it may go
+ * below a depth-1 node (bits 4-7 of flags; 0 = off: the games of the flag left out, byte for byte; at most 8). Without it a
+ * horizon node is worth its static evaluation, in the middle of an exchange or not. With it, at depth 1 every child c is
+ * worth -quiesce(c, stand = its static evaluation, window, q):
+ *   quiesce: q == 0 -> stand; stand >= beta -> stand (decided without expanding c); else c is expanded (one node of the
+ *   budget, like any expansion) for its CANDIDATES - every legal move in check, else the noisy ones (spx_movegen_modes, mode
+ *   1); in check without a candidate -> mated at this ply; in check there is no stand pat, else best = stand and alpha =
+ *   max(alpha, stand) (no candidate: stand; stalemate is not detected, as in the reference); the candidates by (value
+ *   descending, move word ascending), each worth -quiesce(child, its static evaluation, -beta, -alpha, q - 1), fail-soft,
+ *   cut-off at alpha >= beta.
+ * The node budget is still looked at only when an iteration ends, so quiescence nodes lengthen a search beyond k the way any
+ * overshoot does; stats.steps counts them, stats.evals counts the candidates evaluated. Not part of it (later work): SEE
+ * pruning, futility margins, the evasion cap, a transposition table, draw detection inside the tree. q more arena slots per
+ * game. SPX_ERR_INVALID_ARG: q > 8; q > 0 with k <= 1 (the depth-1 policy keeps playing the depth-1 games) or with
+ * SPX_SELFPLAY_HOST_MOVEGEN. The rules in full are with SearchStepParams in csrc/spx_kernels.h and restated in
+ * tests/_qsearch_rules.py. */
+#define SPX_SELFPLAY_QUIESCE_PLIES(q) (((uint32_t)(q) & 15u) << 4)
 typedef struct spx_selfplay_stats {
     uint64_t games, positions, evals, steps;
     uint64_t outcomes[3];    /* white loss / draw / white win (datagen/common.h:24-28) */

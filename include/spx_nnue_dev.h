@@ -62,6 +62,11 @@ int spx_viri_random_game(uint64_t seed, int plies, int dfrc, void* buf, size_t c
  * rows from-scratch rebuilds of those served perspectives would have applied. Synchronises the device and clears them. */
 int spx_debug_refresh_table_stats(spx_ctx* ctx, uint64_t out[4]);
 
+/* The context's last self-play run with a live search (spx_selfplay_run, SPX_SELFPLAY_SEARCH_NODES): out[0] main-search nodes
+ * expanded, out[1] quiescence nodes expanded (SPX_SELFPLAY_QUIESCE_PLIES), out[2] children evaluated for the main nodes, out[3]
+ * candidates evaluated for the quiescence nodes. out[0] + out[1] = stats.steps of that run. */
+int spx_debug_selfplay_search_stats(spx_ctx* ctx, uint64_t out[4]);
+
 /* perft of the host chess core (legal move generation check against published counts). */
 uint64_t spx_perft(const char* fen, int depth);
 

@@ -108,6 +108,7 @@ SYMBOLS = {
     "spx_acc_reserve_refresh_tables": (ctypes.c_int, [_P, ctypes.c_size_t]),
     "spx_acc_bind_refresh_tables": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t]),
     "spx_debug_refresh_table_stats": (ctypes.c_int, [_P, _P]),
+    "spx_debug_selfplay_search_stats": (ctypes.c_int, [_P, _P]),
     "spx_acc_refresh": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t]),
     "spx_acc_update": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_size_t]),
     "spx_acc_eval": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P]),
@@ -130,6 +131,8 @@ SYMBOLS = {
                                            ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     "spx_movegen": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "spx_movegen_device": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
+    "spx_movegen_modes": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "spx_movegen_modes_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
     "spx_pos_legal_moves": (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "spx_host_alloc": (_P, [ctypes.c_size_t]),
     "spx_host_free": (None, [_P]),

@@ -224,6 +224,7 @@ struct spx_ctx {
     size_t streamAccMin = 0;       // spx_update_kernel: records from which the arena is accessed non-temporally
     size_t updateChainMax = 1024;  // option update_chain_max: fused update batches up to this size take spx_update_chain_kernel on
                                    // unit paths (one launch, rebuilds inline); larger ones spx_update_kernel + the rebuild pass
+    uint64_t selfplaySearchStats[4] = {0, 0, 0, 0};  // the last searching self-play run (spx_debug_selfplay_search_stats)
     int64_t selfplayOptions[3] = {1, 0, 0};  // options selfplay_graph (0: direct launches), selfplay_graph_plies (0: automatic), selfplay_trace
     int replayPaths = -1;          // option replay_paths: spx_acc_replay_tree by heavy paths (1) / by levels (0) / its own choice (-1)
     uint32_t replaySegment = 8;    // option replay_segment: plies per path segment of the replay
@@ -272,6 +273,10 @@ uint8_t* ctxSlotRecords(const spx_ctx* ctx) {
 
 int64_t ctxSelfplayOption(const spx_ctx* ctx, int which) {
     return ctx->selfplayOptions[which];
+}
+
+void ctxSetSelfplaySearchStats(spx_ctx* ctx, const uint64_t stats[4]) {
+    std::memcpy(ctx->selfplaySearchStats, stats, sizeof(ctx->selfplaySearchStats));
 }
 }  // namespace spx
 
@@ -1505,6 +1510,15 @@ int spx_acc_bind_refresh_tables(spx_ctx* ctx, const uint32_t* slots, const uint3
     }
     for (size_t i = 0; i < n; ++i) ctx->slotTable[slots[i]] = tables[i];
     SPX_HIP(hipMemcpy(ctx->dSlotTable, ctx->slotTable.data(), ctx->nSlots * 4, hipMemcpyHostToDevice));
+    return SPX_OK;
+}
+
+int spx_debug_selfplay_search_stats(spx_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) {
+        setError("spx_debug_selfplay_search_stats: invalid argument");
+        return SPX_ERR_INVALID_ARG;
+    }
+    std::memcpy(out, ctx->selfplaySearchStats, 4 * 8);
     return SPX_OK;
 }
 
@@ -2893,6 +2907,13 @@ int spx_pos_legal_moves(const spx_packed_pos* pos, uint16_t* moves, spx_packed_p
 int spx_movegen_device(spx_ctx* ctx, const void* d_positions, size_t n, const void* d_parent_values, void* d_children,
                        void* d_moves, void* d_parents, void* d_first, void* d_count, void* d_in_check, size_t capacity,
                        void* d_total, void* stream) {
+    return spx_movegen_modes_device(ctx, d_positions, nullptr, n, d_parent_values, d_children, d_moves, d_parents, d_first,
+                                    d_count, d_in_check, capacity, d_total, stream);
+}
+
+int spx_movegen_modes_device(spx_ctx* ctx, const void* d_positions, const void* d_modes, size_t n, const void* d_parent_values,
+                             void* d_children, void* d_moves, void* d_parents, void* d_first, void* d_count, void* d_in_check,
+                             size_t capacity, void* d_total, void* stream) {
     if (!ctx || (n && (!d_positions || !d_children || !d_moves || !d_parents || !d_first || !d_count || !d_in_check)) ||
         !d_total || n > (1ull << 30) || capacity > 0xFFFFFFFFull) {
         setError("spx_movegen_device: invalid argument");
@@ -2914,6 +2935,7 @@ int spx_movegen_device(spx_ctx* ctx, const void* d_positions, size_t n, const vo
     mp.inCheck = static_cast<uint8_t*>(d_in_check);
     mp.cursor = static_cast<uint32_t*>(d_total);
     mp.capacity = uint32_t(capacity);
+    mp.modes = static_cast<const uint8_t*>(d_modes);
     uint32_t blocks = uint32_t((n + 3) / 4);
     if (blocks > ctx->ftGridCap) blocks = ctx->ftGridCap;
     SPX_HIP(launchMovegen(mp, blocks, s));
@@ -2923,6 +2945,13 @@ int spx_movegen_device(spx_ctx* ctx, const void* d_positions, size_t n, const vo
 int spx_movegen(spx_ctx* ctx, const spx_packed_pos* positions, size_t n, const uint32_t* parent_values,
                 spx_packed_pos* children, uint16_t* moves, uint32_t* parents, uint32_t* first, uint32_t* count,
                 uint8_t* in_check, size_t capacity, size_t* total) {
+    return spx_movegen_modes(ctx, positions, nullptr, n, parent_values, children, moves, parents, first, count, in_check,
+                             capacity, total);
+}
+
+int spx_movegen_modes(spx_ctx* ctx, const spx_packed_pos* positions, const uint8_t* modes, size_t n,
+                      const uint32_t* parent_values, spx_packed_pos* children, uint16_t* moves, uint32_t* parents,
+                      uint32_t* first, uint32_t* count, uint8_t* in_check, size_t capacity, size_t* total) {
     if (!ctx || !total || (n && (!positions || !children || !moves || !parents || !first || !count || !in_check))) {
         setError("spx_movegen: null argument");
         return SPX_ERR_INVALID_ARG;
@@ -2945,6 +2974,7 @@ int spx_movegen(spx_ctx* ctx, const spx_packed_pos* positions, size_t n, const u
     } scratch;
     void* dPos = scratch.get(n * 32);
     void* dPv = parent_values ? scratch.get(n * 4) : nullptr;
+    void* dModes = modes ? scratch.get(n) : nullptr;
     void* dChildren = scratch.get(capacity * 32);
     void* dMoves = scratch.get(capacity * 2);
     void* dParents = scratch.get(capacity * 4);
@@ -2952,14 +2982,15 @@ int spx_movegen(spx_ctx* ctx, const spx_packed_pos* positions, size_t n, const u
     void* dCount = scratch.get(n * 4);
     void* dCheck = scratch.get(n);
     void* dTotal = scratch.get(4);
-    if (!dPos || (parent_values && !dPv) || !dChildren || !dMoves || !dParents || !dFirst || !dCount || !dCheck || !dTotal) {
+    if (!dPos || (parent_values && !dPv) || (modes && !dModes) || !dChildren || !dMoves || !dParents || !dFirst || !dCount || !dCheck || !dTotal) {
         setError("spx_movegen: out of device memory");
         return SPX_ERR_HIP;
     }
     hipStream_t s = ctx->stream;
     SPX_HIP(hipMemcpyAsync(dPos, positions, n * 32, hipMemcpyHostToDevice, s));
     if (parent_values) SPX_HIP(hipMemcpyAsync(dPv, parent_values, n * 4, hipMemcpyHostToDevice, s));
-    const int rc = spx_movegen_device(ctx, dPos, n, dPv, dChildren, dMoves, dParents, dFirst, dCount, dCheck, capacity,
+    if (modes) SPX_HIP(hipMemcpyAsync(dModes, modes, n, hipMemcpyHostToDevice, s));
+    const int rc = spx_movegen_modes_device(ctx, dPos, dModes, n, dPv, dChildren, dMoves, dParents, dFirst, dCount, dCheck, capacity,
                                       dTotal, s);
     if (rc != SPX_OK) return rc;
     uint32_t produced = 0;

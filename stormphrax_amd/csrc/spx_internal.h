@@ -22,6 +22,7 @@ namespace spx {
 size_t ctxMaxBatch(const spx_ctx* ctx);
 int ctxDevice(const spx_ctx* ctx);
 void* ctxStream(const spx_ctx* ctx);  // the context's own hipStream_t (what a NULL stream argument means)
+void ctxSetSelfplaySearchStats(spx_ctx* ctx, const uint64_t stats[4]);  // main nodes, quiescence nodes, their children / candidates
 int64_t ctxSelfplayOption(const spx_ctx* ctx, int which);  // 0 selfplay_graph, 1 selfplay_graph_plies, 2 selfplay_trace (spx_ctx_set_option)
 uint8_t* ctxSlotRecords(const spx_ctx* ctx);  // device pointer: the arena's [nSlots][32] record store (after spx_acc_reserve)
 // lanes: see spx_api.cpp (two scratch sets + streams; big kernels chained by events)

@@ -122,6 +122,8 @@ struct MovegenParams {              // spx_movegen_kernel (spx_movegen.hip)
     uint8_t* inCheck;               // [nPositions] side to move in check (mate vs stalemate when count == 0)
     uint32_t* cursor;               // running child count, zero on entry; may end above capacity (= overflow)
     uint32_t capacity;
+    const uint8_t* modes;           // nullable, [nPositions]: 0 = every legal move; 1 = the quiescence set (every legal move in
+                                    // check, else the noisy ones - Position::isNoisy; `count` = the candidates)
 };
 
 struct PickParams {                 // spx_pick_kernel (spx_movegen.hip): one uniformly random legal move per position
@@ -150,7 +152,7 @@ struct SelfplayCounters {   // one per run, device memory, shared by the halves;
     uint32_t started;       // games counted towards the target (begun and not discarded by the verification filter)
     uint32_t poolCursor;    // openings taken from the pool so far
     uint32_t poolSize;      // openings the host has published so far (ring: entry i lives at i % poolCap)
-    uint32_t reserved;
+    uint32_t searchErrors;  // search levels found outside a seat's frames (clamped; the host ends the run with an error)
 };
 static_assert(sizeof(SelfplayCounters) % 8 == 0 && sizeof(SelfplayCounters) / 8 < 62, "spx_game_status_kernel copies it in 64-bit words");
 
@@ -201,7 +203,24 @@ struct GameStepParams {
 //     the score is decisive (core.h:722-724); the root's own expansion is shared by all iterations
 //   K <= 1: the depth-1 policy of spx_game_step_kernel (incl. its temperature), move for move
 // No transposition table, no repetition / 50-move detection inside the tree (the game loop's own rules apply to the moves played).
-constexpr uint32_t kSearchLevels = 8;       // frames per seat: the root (level 0) .. level 7
+//
+// QUIESCENCE (SPX_SELFPLAY_QUIESCE_PLIES(Q), 1 <= Q <= kQuiesceMaxPlies, needs K >= 2; the role of qsearch,
+// search.cpp:1451-1640; restated in tests/_qsearch_rules.py). The depth-1 line of search() becomes
+//     depth == 1: x = -quiesce(c, stand = -value(c), -beta, -alpha, ply + 1, Q) for each child c, fail-soft as at depth >= 2
+//   quiesce(c, stand, a, b, ply, q)           c has NOT been expanded; stand = net(c) clamped, from c's mover
+//     q == 0      -> stand                     (horizon)
+//     stand >= b  -> stand                     (stand-pat cut-off, decided WITHOUT expanding c: its check status is unknown)
+//     expand c in quiescence mode (one node, like any expansion): in_check and the CANDIDATES - every legal move when in
+//       check, else the noisy legal moves (Position::isNoisy, position.cpp:683-689; MovegenParams::modes)
+//     in check, no candidate -> -(kScoreMate - ply);  in check -> best = -INF (no stand pat, search.cpp:1513-1516)
+//     else best = stand, a = max(a, stand)     (no candidate: stand; stalemate is not detected, search.cpp:1634)
+//     candidates in order (value descending, move word ascending): x = -quiesce(child, -value(child), -b, -a, ply + 1, q - 1),
+//       fail-soft update, stop at a >= b;  return best
+// Every expansion counts one node; the budget is still looked at only when an iteration ends at the root. Levels per seat:
+// kSearchLevels + Q. NOT here (later work): SEE pruning, futility margins, the "two legal moves then stop" rule of evasions,
+// a transposition table, draw detection inside the tree.
+constexpr uint32_t kSearchLevels = 8;       // frames per seat of the main search: the root (level 0) .. level 7
+constexpr uint32_t kQuiesceMaxPlies = 8;    // most quiescence plies a caller may ask for (levels 8 .. 7 + Q)
 constexpr uint32_t kSearchChildren = 224;   // children kept per frame (the legal maximum is 218)
 constexpr int32_t kSearchInf = 32767, kSearchMate = 32766;  // core.h:705-706
 struct SearchSeat {          // one per seat
@@ -211,10 +230,10 @@ struct SearchSeat {          // one per seat
     int32_t prevBest;        // root child the last completed iteration chose (-1: none yet)
 };
 struct SearchFrame {         // one per seat and level, 64 bytes
-    uint32_t count, depth;   // children; remaining depth (>= 1)
+    uint32_t count, depth;   // children; remaining depth (>= 1; 0 = a quiescence frame)
     int32_t alpha, beta, best, bestIdx;
     int32_t cur;             // the child being searched below this frame
-    uint32_t reserved;
+    uint32_t reserved;       // quiescence frame: stand pat (low 16 bits, signed) | quiescence plies left at it << 16
     uint64_t visited[4];     // children already searched in this visit
 };
 struct SearchStepParams {
@@ -222,14 +241,21 @@ struct SearchStepParams {
                                     //  moves / children: this round's batch, i.e. the children of every seat's `pending` node)
     uint32_t nodeBudget;            // K
     SearchSeat* seats;              // [nSeats]
-    SearchFrame* frames;            // [nSeats][kSearchLevels]
-    uint64_t* frameRecords;         // [nSeats][kSearchLevels][kSearchChildren] records as u64[4]
-    int32_t* frameValues;           // [nSeats][kSearchLevels][kSearchChildren]
-    uint16_t* frameWords;           // [nSeats][kSearchLevels][kSearchChildren] viriformat move words
+    SearchFrame* frames;            // [nSeats][levels]
+    uint64_t* frameRecords;         // [nSeats][levels][kSearchChildren] records as u64[4]
+    int32_t* frameValues;           // [nSeats][levels][kSearchChildren]
+    uint16_t* frameWords;           // [nSeats][levels][kSearchChildren] viriformat move words
     uint64_t* pending;              // [nSeats] records: the node each seat expands next (the next move generation's input)
     uint32_t* pendingSlots;         // [nSeats] its accumulator slot
     uint32_t levelSlotBase;         // accumulator slot of (seat, level L >= 1) = levelSlotBase + (L - 1) * nSeatsTotal + seat
-    unsigned long long* expansions; // run-wide count of expanded nodes
+    unsigned long long* expansions; // [nSeats]: nodes expanded so far (both kinds)
+    // (quiescence: after everything the default instantiation reads, whose argument offsets therefore stay what they were)
+    uint32_t quiescePlies;          // Q (0 = none: the default instantiation of the kernel)
+    uint32_t levels;                // frames per seat = kSearchLevels + Q
+    uint8_t* pendingModes;          // Q >= 1, [nSeats]: MovegenParams::modes of the next move generation (1 = `pending` is a
+                                    // quiescence node)
+    unsigned long long* quiesceExpansions;  // Q >= 1, [nSeats][3]: the expansions that were quiescence nodes, their candidates,
+                                            // the children of all expansions (spx_debug_selfplay_search_stats)
 };
 
 struct ViriExpandParams {          // spx_viri_expand_kernel (spx_movegen.hip)

@@ -171,6 +171,12 @@ __device__ void writeChild(const Parent& p, const Sets& s, int from, int to, int
 
 constexpr int kMaxItems = 256;  // pseudo-legal moves of one position (the legal maximum is 218)
 
+// kModes = MovegenParams::modes is given: a position of mode 1 yields its QUIESCENCE SET - every legal move when the side to
+// move is in check, else the noisy legal moves (Position::isNoisy, position.cpp:683-689: not castling, and en passant, a
+// queen promotion or an occupied target square; an under-promotion only when it captures). The legal flag of every other
+// item is dropped before counting and placement, so the candidates keep the relative order of the full generation. The
+// default instantiation (kModes = false) is the kernel without any of this.
+template <bool kModes>
 __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
     __shared__ uint16_t sItems[4][kMaxItems];
     const uint32_t lane = laneId();
@@ -210,6 +216,12 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
         const int kingSq = ownKing ? ctz64(ownKing) : 0;
         const bool mine = occupied && (isWhite == (us == 1));
         const int from = int(lane);
+        // quiescence set wanted and the side to move not in check: only the noisy moves are candidates (wave-uniform)
+        bool noisyOnly = false;
+        if (kModes) {
+            const uint32_t mode = uint32_t(__builtin_amdgcn_readfirstlane(int(p.modes[it])));
+            noisyOnly = mode == 1u && !attackedBy(s, kingSq, them, s.occ, 0);
+        }
 
         // ---- pseudo-legal targets of this lane's piece (generatePseudo, spx_chess.cpp:249-318) ----
         uint64_t targets = 0;
@@ -271,8 +283,9 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
                 const uint64_t capBit = isEp ? (1ull << (to + (us ? -8 : 8))) : (s.occ & (1ull << to));
                 const uint64_t occ2 = (s.occ & ~(1ull << f) & ~capBit) | (1ull << to);
                 const int ksq2 = fType == 5 ? to : kingSq;
-                const bool ok = !attackedBy(s, ksq2, them, occ2, capBit);
-                children = ok ? (isPromo ? 4u : 1u) : 0u;
+                bool ok = !attackedBy(s, ksq2, them, occ2, capBit);
+                if (kModes && noisyOnly) ok = ok && (capBit != 0 || isPromo);  // (capBit covers en passant)
+                children = ok ? (isPromo && !(kModes && noisyOnly && capBit == 0) ? 4u : 1u) : 0u;
                 sItems[wave][i] = uint16_t(item | (ok ? 0x1000u : 0u) | (isPromo ? 0x2000u : 0u) | (isEp ? 0x4000u : 0u));
             }
 #pragma unroll
@@ -283,7 +296,7 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
         {
             uint32_t castleOk = 0;
             int castleRook[2] = {-1, -1};
-            if (mine && type == 5) {
+            if (mine && type == 5 && !(kModes && noisyOnly)) {  // (never a quiescence candidate: illegal in check, quiet otherwise)
                 const uint64_t myRooks = rightsBb & own;
                 const uint64_t kingside = myRooks & ~below(from) & ~(1ull << from), queenside = myRooks & below(from);
                 // unpackBoard keeps the LAST (highest) flagged rook per side (spx_chess.cpp:708-717)
@@ -337,7 +350,9 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
             const uint32_t item = i < nItems ? sItems[wave][i] : 0u;
             const bool legal = (item & 0x1000u) != 0;
             const bool isPromo = (item & 0x2000u) != 0;
-            const uint32_t mineCount = legal ? (isPromo ? 4u : 1u) : 0u;
+            // a quiet promotion in a quiescence set: the queen alone (it is written first)
+            const bool queenOnly = kModes && noisyOnly && isPromo && !((s.occ >> ((item >> 6) & 63u)) & 1);
+            const uint32_t mineCount = legal ? (isPromo && !queenOnly ? 4u : 1u) : 0u;
             uint32_t incl = mineCount;
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
@@ -349,7 +364,7 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
                 uint32_t k = base + done + incl - mineCount;
                 const int f = int(item & 63), to = int((item >> 6) & 63);
                 if (isPromo) {
-                    for (int pt = 4; pt >= 1; --pt) {
+                    for (int pt = 4; pt >= (queenOnly ? 4 : 1); --pt) {
                         writeChild(par, s, f, to, kChildPromotion, pt, p.children + size_t(k) * 4, p.moves + k);
                         p.parents[k] = parentValue;
                         ++k;
@@ -679,8 +694,22 @@ __device__ __forceinline__ long long waveMax(long long v) {
     return v;
 }
 
+// kQuiesce (SPX_SELFPLAY_QUIESCE_PLIES(Q), Q >= 1): the children of a depth-1 frame and of a quiescence frame are resolved by
+// quiesce(). Such a frame visits its children in descending value, and a child with value <= alpha (its stand pat cuts off)
+// or without quiescence plies left returns its value without a round of its own; once one child is such a child every
+// later one is too and none can raise `best` above it, so the frame is finished on the spot. Only a child with value >
+// alpha and plies left costs a round: it becomes a QUIESCENCE FRAME (depth 0; its stand pat and remaining plies travel in
+// SearchFrame::reserved, its window in alpha / beta as entered) whose expansion asks the move generator for the quiescence
+// set (pendingModes = 1); whether the stand pat applies is decided when the expansion comes back with in_check.
+// The default instantiation (kQuiesce = false) is the kernel without any of this, its level stride the constant.
+__device__ __forceinline__ uint32_t packQuiesce(int32_t stand, uint32_t plies) {
+    return (uint32_t(stand) & 0xFFFFu) | (plies << 16);
+}
+
+template <bool kQuiesce>
 __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams sp) {
     const GameStepParams& p = sp.game;
+    const uint32_t levels = kQuiesce ? sp.levels : kSearchLevels;
     const uint32_t lane = laneId();
     const uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (g >= p.nSeats) return;
@@ -692,14 +721,14 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
     const uint32_t seat = p.seatBase + g;
     const uint32_t oldSlot = uniform(p.slots[g]);
     const uint32_t otherSlot = oldSlot == seat ? p.nSeatsTotal + seat : seat;
-    SearchFrame* frames = sp.frames + size_t(g) * kSearchLevels;
-    uint64_t* fRecords = sp.frameRecords + size_t(g) * kSearchLevels * kSearchChildren * 4;
-    int32_t* fValues = sp.frameValues + size_t(g) * kSearchLevels * kSearchChildren;
-    uint16_t* fWords = sp.frameWords + size_t(g) * kSearchLevels * kSearchChildren;
+    SearchFrame* frames = sp.frames + size_t(g) * levels;
+    uint64_t* fRecords = sp.frameRecords + size_t(g) * levels * kSearchChildren * 4;
+    int32_t* fValues = sp.frameValues + size_t(g) * levels * kSearchChildren;
+    uint16_t* fWords = sp.frameWords + size_t(g) * levels * kSearchChildren;
 
     MoveResult mr{kNoOutcome, false, false, 0, 0};
     uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;  // the chosen child when a move is played / the next node when the search goes on
-    bool descend = false;
+    bool descend = false, quiesceNext = false;
     uint32_t nextLevel = 0;
     if (st.active) {
         const uint32_t count = min(uniform(p.count[g]), kSearchChildren);
@@ -711,6 +740,10 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
             ss.nodes += 1;
             if (lane == 0) sp.expansions[g] += 1;
             uint32_t L = ss.top;
+            if (kQuiesce && L >= levels) {  // a corrupted level must not walk off the seat's frames: the host ends the run
+                L = levels - 1;
+                if (lane == 0) atomicAdd(&p.counters->searchErrors, 1u);
+            }
             const uint32_t batchLevel = L;  // the frame whose children are this round's batch (its storage is written below:
                                             // reads of it in THIS round go to the batch instead)
             // the running frame lives in registers (wave-uniform); frames are read from memory when a child returns into them
@@ -719,13 +752,30 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
             int32_t fAlpha = frames[L].alpha, fBeta = frames[L].beta, fBest = -kSearchInf, fBestIdx = -1, fCur = -1;
             uint64_t v0 = 0, v1 = 0, v2 = 0, v3 = 0;  // visited
             fDepth = uniform(fDepth), fAlpha = int32_t(uniform(uint32_t(fAlpha))), fBeta = int32_t(uniform(uint32_t(fBeta)));
+            // (kQuiesce) a quiescence frame's stand pat and the quiescence plies left AT it (>= 1: it was expanded)
+            int32_t fStand = 0;
+            uint32_t fPlies = 0;
+            if (kQuiesce) {
+                const uint32_t packed = uniform(frames[L].reserved);
+                fStand = int32_t(int16_t(packed & 0xFFFFu)), fPlies = (packed >> 16) & 15u;
+            }
+            const bool quiesceNode = kQuiesce && fDepth == 0;
+            if (kQuiesce && lane == 0) {
+                if (quiesceNode) sp.quiesceExpansions[3 * g] += 1, sp.quiesceExpansions[3 * g + 1] += count;
+                sp.quiesceExpansions[3 * g + 2] += count;
+            }
             int32_t res = 0;
             enum { kReturn, kDescend, kPlay } action;
-            if (count == 0) {
-                res = inCheck ? -(kSearchMate - int32_t(L)) : 0;
+            if (count == 0) {  // (a quiescence node out of check: no candidate - the stand pat; stalemate is not detected)
+                res = inCheck ? -(kSearchMate - int32_t(L)) : (quiesceNode ? fStand : 0);
                 action = kReturn;
             } else {
-                if (L == 0 || fDepth >= 2) {  // the children stay: the root's always (the move played comes from them)
+                if (quiesceNode && !inCheck) {  // stand pat (none in check: search.cpp:1513-1516)
+                    fBest = fStand;
+                    fAlpha = max(fAlpha, fStand);
+                }
+                // the children stay: the root's always (the move played comes from them); with quiescence a depth-1 frame's too
+                if (L == 0 || fDepth >= 2 || kQuiesce) {
                     for (uint32_t k = lane; k < count; k += 64) {
                         const size_t at = size_t(L) * kSearchChildren + k;
                         fValues[at] = clampStaticEval(-p.evals[lo + k]);
@@ -733,7 +783,7 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                         for (int w = 0; w < 4; ++w) fRecords[at * 4 + w] = p.children[size_t(lo + k) * 4 + w];
                     }
                 }
-                if (fDepth == 1) {
+                if (!kQuiesce && fDepth == 1) {
                     long long key = INT64_MIN;
                     for (uint32_t k = lane; k < count; k += 64) {
                         const long long mine = childKey(clampStaticEval(-p.evals[lo + k]), p.moves[lo + k]);
@@ -764,6 +814,10 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                     fAlpha = int32_t(uniform(uint32_t(f.alpha))), fBeta = int32_t(uniform(uint32_t(f.beta)));
                     fBest = int32_t(uniform(uint32_t(f.best))), fBestIdx = int32_t(uniform(uint32_t(f.bestIdx)));
                     fCur = int32_t(uniform(uint32_t(f.cur)));
+                    if (kQuiesce) {
+                        const uint32_t packed = uniform(f.reserved);
+                        fStand = int32_t(int16_t(packed & 0xFFFFu)), fPlies = (packed >> 16) & 15u;
+                    }
                     v0 = f.visited[0], v1 = f.visited[1], v2 = f.visited[2], v3 = f.visited[3];
                     const int32_t v = -res;
                     if (v > fBest) fBest = v, fBestIdx = fCur;
@@ -814,6 +868,32 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                 }
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) idx = min(idx, uint32_t(__shfl_xor(idx, off, 64)));
+                uint32_t childPlies = 0;  // (kQuiesce) quiescence plies left at the child
+                if (kQuiesce && fDepth <= 1) {
+                    const int32_t v = int32_t(top >> 16);
+                    childPlies = fDepth == 1 ? sp.quiescePlies : fPlies - 1;
+                    bool now = childPlies == 0 || v <= fAlpha;  // horizon / stand-pat cut-off: this child and every later one
+                    if (!now && L + 1 >= levels) {               // (cannot happen: levels = kSearchLevels + Q)
+                        now = true;
+                        if (lane == 0) atomicAdd(&p.counters->searchErrors, 1u);
+                    }
+                    if (now) {
+                        if (v > fBest) fBest = v, fBestIdx = int32_t(idx);
+                        res = fBest;
+                        action = kReturn;
+                        continue;
+                    }
+                    quiesceNext = true;
+                }
+                // the descend itself, whatever the frame's stored depth says (a clamped level whose frame is garbage): nothing is
+                // written at level `levels`. (kQuiesce only: the default instantiation is the kernel as it was, its main search
+                // bounded by iter <= kSearchLevels.)
+                if (kQuiesce && L + 1 >= levels) {
+                    if (lane == 0) atomicAdd(&p.counters->searchErrors, 1u);
+                    res = fBest;
+                    action = kReturn;
+                    continue;
+                }
                 const uint64_t bit = 1ull << (idx & 63);
                 v0 |= idx < 64 ? bit : 0ull;
                 v1 |= (idx >= 64 && idx < 128) ? bit : 0ull;
@@ -824,11 +904,16 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                     SearchFrame f{};
                     f.count = fCount, f.depth = fDepth, f.alpha = fAlpha, f.beta = fBeta, f.best = fBest, f.bestIdx = fBestIdx;
                     f.cur = fCur;
+                    if (kQuiesce) f.reserved = packQuiesce(fStand, fPlies);
                     f.visited[0] = v0, f.visited[1] = v1, f.visited[2] = v2, f.visited[3] = v3;
                     frames[L] = f;
                     SearchFrame below{};
                     below.depth = fDepth - 1, below.alpha = -fBeta, below.beta = -fAlpha, below.best = -kSearchInf;
                     below.bestIdx = below.cur = -1;
+                    if (kQuiesce && quiesceNext) {
+                        const int32_t v = int32_t(top >> 16);
+                        below.depth = 0, below.reserved = packQuiesce(-v, childPlies);
+                    }
                     frames[L + 1] = below;
                 }
                 const uint64_t* rec = fromBatch ? p.children + size_t(lo + idx) * 4
@@ -874,6 +959,7 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
         p.updParents[g] = descend ? parentSlot : (mr.moved ? oldSlot : 2u * p.nSeatsTotal);
         p.updChildren[g] = descend ? levelSlot : otherSlot;
         sp.pendingSlots[g] = descend ? levelSlot : otherSlot;
+        if (kQuiesce) sp.pendingModes[g] = descend && quiesceNext ? 1 : 0;
         if (newRoot) {
             p.slots[g] = otherSlot;
             SearchFrame root{};
@@ -1023,7 +1109,8 @@ hipError_t launchGameStep(const GameStepParams& p, hipStream_t stream) {
 }
 
 hipError_t launchSearchStep(const SearchStepParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL(spx_search_step_kernel, dim3((p.game.nSeats + 3) / 4), dim3(256), 0, stream, p);
+    if (p.quiescePlies) hipLaunchKernelGGL(spx_search_step_kernel<true>, dim3((p.game.nSeats + 3) / 4), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(spx_search_step_kernel<false>, dim3((p.game.nSeats + 3) / 4), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -1033,7 +1120,8 @@ hipError_t launchPick(const PickParams& p, hipStream_t stream) {
 }
 
 hipError_t launchMovegen(const MovegenParams& p, uint32_t gridBlocks, hipStream_t stream) {
-    hipLaunchKernelGGL(spx_movegen_kernel, dim3(gridBlocks), dim3(256), 0, stream, p);
+    if (p.modes) hipLaunchKernelGGL(spx_movegen_kernel<true>, dim3(gridBlocks), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(spx_movegen_kernel<false>, dim3(gridBlocks), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

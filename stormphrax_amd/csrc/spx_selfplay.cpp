@@ -855,8 +855,10 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     // spx_search_step_kernel in place of spx_game_step_kernel and one more accumulator slot per seat and tree level.
     const uint32_t searchNodes = p->flags >> 8;
     const bool search = searchNodes != 0;
+    const uint32_t quiescePlies = (p->flags >> 4) & 15u;  // SPX_SELFPLAY_QUIESCE_PLIES (checked by spx_selfplay_run)
+    const uint32_t levels = kSearchLevels + quiescePlies;  // frames and level slots per seat
     // two slots per seat (current / next position) + the null slot (+ the search levels below the root)
-    int rc = spx_acc_reserve(ctx, size_t(G) * 2 + 1 + (search ? size_t(G) * (kSearchLevels - 1) : 0));
+    int rc = spx_acc_reserve(ctx, size_t(G) * 2 + 1 + (search ? size_t(G) * (levels - 1) : 0));
     if (rc != SPX_OK) return rc;
     SPX_SP_HIP(hipSetDevice(ctxDevice(ctx)));
     SPX_SP_HIP(hipMemset(ctxSlotRecords(ctx) + size_t(G) * 2 * 32, 0, 32));  // the null slot holds the empty board
@@ -865,7 +867,7 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
         // the seat's current / next slots s, G + s and its search levels 2 G + 1 + (L - 1) G + s
         rc = spx_acc_reserve_refresh_tables(ctx, G);
         if (rc != SPX_OK) return rc;
-        const size_t perSeatSlots = 2 + (search ? kSearchLevels - 1 : 0);
+        const size_t perSeatSlots = 2 + (search ? levels - 1 : 0);
         std::vector<uint32_t> bindSlots, bindTables;
         bindSlots.reserve(size_t(G) * perSeatSlots);
         bindTables.reserve(size_t(G) * perSeatSlots);
@@ -893,6 +895,10 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
         }
     } closer{out};
     std::memset(stats, 0, sizeof(*stats));
+    {
+        const uint64_t none[4] = {0, 0, 0, 0};  // (spx_debug_selfplay_search_stats speaks of THIS run, search or not)
+        ctxSetSelfplaySearchStats(ctx, none);
+    }
 
     const size_t perSeat = 96;  // children per seat and ply (mean ~35; a ply that needs more is reported as an error)
     // Plies per captured graph. Between two graph launches on a stream this runtime leaves ~80-100 us (rocprofv3 kernel trace,
@@ -929,9 +935,9 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     auto* hPoolRecords = pinned.get<spx_packed_pos>(16384);
     auto* hPoolSeeds = pinned.get<uint64_t>(16384);
     auto* hPoolSize = pinned.get<uint32_t>(1);
-    // search mode: the seats' stacks (57 KiB of child records per seat and level: 1.8 GiB at 4 096 seats - HBM is not the
-    // scarce resource here), the nodes to expand next and their slots
-    const size_t frameSlots = search ? size_t(G) * kSearchLevels : 0;
+    // search mode: the seats' stacks (8.3 KiB of children per seat and level: 0.27 GB at 4 096 seats and 8 levels - HBM is not
+    // the scarce resource here), the nodes to expand next and their slots
+    const size_t frameSlots = search ? size_t(G) * levels : 0;
     auto* dSeats = dev.get<SearchSeat>(search ? G : 0);
     auto* dFrames = dev.get<SearchFrame>(frameSlots);
     auto* dFrameRecords = dev.get<uint64_t>(frameSlots * kSearchChildren * 4);
@@ -940,6 +946,8 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     auto* dPending = dev.get<uint64_t>(search ? size_t(G) * 4 : 0);
     auto* dPendingSlots = dev.get<uint32_t>(search ? G : 0);
     auto* dExpansions = dev.get<unsigned long long>(search ? G : 0);
+    auto* dPendingModes = dev.get<uint8_t>(quiescePlies ? G : 0);
+    auto* dQuiesceExpansions = dev.get<unsigned long long>(quiescePlies ? size_t(G) * 3 : 0);
     std::vector<DeviceHalf> halves(nHalves);
     struct RingCloser {  // the halves' output rings
         std::vector<DeviceHalf>& h;
@@ -951,7 +959,7 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     } ringCloser{halves};
     bool ok = dPositions && dSlots && dRng && dFirst && dCount && dInCheck && dState && dInitial && dGameMoves && dKeys &&
               dPoolRecords && dPoolSeeds && dCounters && hPoolRecords && hPoolSeeds && hPoolSize && dSeats && dFrames &&
-              dFrameRecords && dFrameValues && dFrameWords && dPending && dPendingSlots && dExpansions;
+              dFrameRecords && dFrameValues && dFrameWords && dPending && dPendingSlots && dExpansions && dPendingModes && dQuiesceExpansions;
     for (uint32_t h = 0; h < nHalves && ok; ++h) {
         DeviceHalf& hf = halves[h];
         hf.index = h;
@@ -1018,6 +1026,10 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
         SPX_SP_HIP(hipMemset(dPending, 0, size_t(G) * 32));
         SPX_SP_HIP(hipMemset(dExpansions, 0, size_t(G) * 8));
     }
+    if (quiescePlies) {
+        SPX_SP_HIP(hipMemset(dPendingModes, 0, G));
+        SPX_SP_HIP(hipMemset(dQuiesceExpansions, 0, size_t(G) * 24));
+    }
     SPX_SP_HIP(hipMemset(dPositions, 0, size_t(G) * 32));  // empty records generate no moves
     SPX_SP_HIP(hipMemset(dState, 0, size_t(G) * sizeof(SeatState)));
     SPX_SP_HIP(hipMemset(dRng, 0, size_t(G) * 8));
@@ -1030,7 +1042,7 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     double gpuWait = 0.0, enqueueSeconds = 0.0;
     SelfplayCounters latest{};       // newest counters seen
     uint32_t published = 0;          // openings handed to the device so far
-    uint64_t evals = 0, steps = 0;
+    uint64_t evals = 0, steps = 0, quiesceNodes = 0;
 
     // Openings: generated in bulk on the device (OpeningPool), published to the device-side ring ahead of every claim the
     // step kernels in flight can make: a step claims at most one opening per seat, and up to 2 * kStatusSlots half-steps may
@@ -1080,6 +1092,7 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
             mp.inCheck = dInCheck + hf.begin;
             mp.cursor = hf.dTotal;
             mp.capacity = uint32_t(hf.cap);
+            mp.modes = quiescePlies ? dPendingModes + hf.begin : nullptr;  // (a quiescence node wants its candidates only)
             SPX_SP_HIP(launchMovegen(mp, (seats + 3) / 4, s));
         }
         // eval-only children (child slots NULL): ~35 siblings per seat evaluated, none stored
@@ -1120,14 +1133,18 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
             sp.game = gp;
             sp.nodeBudget = searchNodes;
             sp.seats = dSeats + hf.begin;
-            sp.frames = dFrames + size_t(hf.begin) * kSearchLevels;
-            sp.frameRecords = dFrameRecords + size_t(hf.begin) * kSearchLevels * kSearchChildren * 4;
-            sp.frameValues = dFrameValues + size_t(hf.begin) * kSearchLevels * kSearchChildren;
-            sp.frameWords = dFrameWords + size_t(hf.begin) * kSearchLevels * kSearchChildren;
+            sp.quiescePlies = quiescePlies;
+            sp.levels = levels;
+            sp.frames = dFrames + size_t(hf.begin) * levels;
+            sp.frameRecords = dFrameRecords + size_t(hf.begin) * levels * kSearchChildren * 4;
+            sp.frameValues = dFrameValues + size_t(hf.begin) * levels * kSearchChildren;
+            sp.frameWords = dFrameWords + size_t(hf.begin) * levels * kSearchChildren;
             sp.pending = dPending + size_t(hf.begin) * 4;
             sp.pendingSlots = dPendingSlots + hf.begin;
             sp.levelSlotBase = 2 * G + 1;
             sp.expansions = dExpansions + hf.begin;
+            sp.pendingModes = quiescePlies ? dPendingModes + hf.begin : nullptr;
+            sp.quiesceExpansions = quiescePlies ? dQuiesceExpansions + size_t(hf.begin) * 3 : nullptr;
             SPX_SP_HIP(launchSearchStep(sp, s));
         } else {
             SPX_SP_HIP(launchGameStep(gp, s));
@@ -1224,6 +1241,11 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
             latest.discarded = std::max(latest.discarded, c.discarded);
             latest.started = std::max(latest.started, c.started);
             latest.poolCursor = std::max(latest.poolCursor, c.poolCursor);
+            latest.searchErrors = std::max(latest.searchErrors, c.searchErrors);
+        }
+        if (latest.searchErrors) {
+            setError("spx_selfplay_run: a search level outside a seat's frames (internal: corrupted search state)");
+            return SPX_ERR_HIP;
         }
         if (latest.poolCursor > published) {
             setError("spx_selfplay_run: the opening pool ran dry (internal: the publishing margin was too small)");
@@ -1285,10 +1307,21 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     stats->evals = evals;
     stats->steps = (steps + nHalves - 1) / nHalves;
     if (search) {  // nodes expanded by all searches together
-        std::vector<unsigned long long> expanded(G);
+        std::vector<unsigned long long> expanded(size_t(G) * 3);
         SPX_SP_HIP(hipMemcpy(expanded.data(), dExpansions, size_t(G) * 8, hipMemcpyDeviceToHost));
         stats->steps = 0;
-        for (unsigned long long e : expanded) stats->steps += e;
+        for (uint32_t g = 0; g < G; ++g) stats->steps += expanded[g];
+        // (without quiescence every child evaluated is a main node's; the tail rounds of drained seats evaluate nothing)
+        uint64_t children = evals, quiesceCandidates = 0;
+        if (quiescePlies) {
+            SPX_SP_HIP(hipMemcpy(expanded.data(), dQuiesceExpansions, size_t(G) * 24, hipMemcpyDeviceToHost));
+            children = 0;
+            for (uint32_t g = 0; g < G; ++g) {
+                quiesceNodes += expanded[3 * g], quiesceCandidates += expanded[3 * g + 1], children += expanded[3 * g + 2];
+            }
+        }
+        const uint64_t split[4] = {stats->steps - quiesceNodes, quiesceNodes, children - quiesceCandidates, quiesceCandidates};
+        ctxSetSelfplaySearchStats(ctx, split);
     }
     stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     stats->gpu_seconds = gpuWait;
@@ -1300,6 +1333,11 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
                                                   : kGraphPlies == 4 ? "graph mode: four plies per launch, two launches ahead"
                                                                      : "graph mode: option selfplay_graph_plies plies per launch, two launches ahead")
                               : "direct launches");
+        if (search) {
+            std::fprintf(stderr, "[spx_selfplay] nodes expanded: %llu main, %llu quiescence (quiescence plies %u)\n",
+                         static_cast<unsigned long long>(stats->steps - quiesceNodes),
+                         static_cast<unsigned long long>(quiesceNodes), quiescePlies);
+        }
     }
     return rc;
 }
@@ -1309,7 +1347,9 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
 extern "C" int spx_selfplay_run(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_path,
                                 spx_selfplay_stats* stats) {
     if (!ctx || !p || !stats || p->n_games == 0 || p->target_games == 0 ||
-        (p->flags & 0xFFu & ~uint32_t(SPX_SELFPLAY_HOST_MOVEGEN | SPX_SELFPLAY_REFRESH_TABLES)) ||
+        (p->flags & 0xFFu & ~uint32_t(SPX_SELFPLAY_HOST_MOVEGEN | SPX_SELFPLAY_REFRESH_TABLES | 0xF0u)) ||
+        ((p->flags >> 4) & 15u) > kQuiesceMaxPlies ||
+        (((p->flags >> 4) & 15u) && ((p->flags >> 8) < 2 || (p->flags & SPX_SELFPLAY_HOST_MOVEGEN))) ||  // quiescence: k >= 2, device
         ((p->flags & SPX_SELFPLAY_HOST_MOVEGEN) && (p->flags >> 8)) ||  // the search lives in the device-resident driver
         ((p->flags & SPX_SELFPLAY_HOST_MOVEGEN) && (p->flags & SPX_SELFPLAY_REFRESH_TABLES))) {  // ... and so do the tables
         setError("spx_selfplay_run: invalid argument");

@@ -206,9 +206,10 @@ class NnueState:
                                       ctypes.byref(games), ctypes.byref(bad)))
         return (out, games.value, bad.value, keep.astype(bool)) if with_filter else (out, games.value, bad.value)
 
-    def movegen(self, positions, parent_values=None, capacity=None):
+    def movegen(self, positions, parent_values=None, capacity=None, modes=None):
         """Legal moves + child records of every position, generated on the device (spx_movegen).
-        -> dict(children, moves, parents, first, count, in_check)."""
+        modes: one byte per position (spx_movegen_modes): 0 = every legal move, 1 = the quiescence set (every legal move in
+        check, else the noisy ones). -> dict(children, moves, parents, first, count, in_check)."""
         pos = np.ascontiguousarray(positions, dtype=PACKED_DTYPE)
         n = pos.shape[0]
         capacity = capacity if capacity is not None else 64 * n + 256
@@ -220,9 +221,17 @@ class NnueState:
         in_check = np.zeros(n, dtype=np.uint8)
         pv = None if parent_values is None else np.ascontiguousarray(parent_values, dtype=np.uint32)
         total = ctypes.c_size_t()
-        check(_lib.load().spx_movegen(self._h, pos.ctypes.data, n, None if pv is None else pv.ctypes.data,
-                                      children.ctypes.data, moves.ctypes.data, parents.ctypes.data, first.ctypes.data,
-                                      count.ctypes.data, in_check.ctypes.data, capacity, ctypes.byref(total)))
+        if modes is None:
+            check(_lib.load().spx_movegen(self._h, pos.ctypes.data, n, None if pv is None else pv.ctypes.data,
+                                          children.ctypes.data, moves.ctypes.data, parents.ctypes.data, first.ctypes.data,
+                                          count.ctypes.data, in_check.ctypes.data, capacity, ctypes.byref(total)))
+        else:
+            md = np.ascontiguousarray(modes, dtype=np.uint8)
+            assert md.shape == (n,)
+            check(_lib.load().spx_movegen_modes(self._h, pos.ctypes.data, md.ctypes.data, n,
+                                                None if pv is None else pv.ctypes.data, children.ctypes.data,
+                                                moves.ctypes.data, parents.ctypes.data, first.ctypes.data, count.ctypes.data,
+                                                in_check.ctypes.data, capacity, ctypes.byref(total)))
         t = total.value
         return {"children": children[:t], "moves": moves[:t], "parents": parents[:t], "first": first, "count": count,
                 "in_check": in_check.astype(bool)}
@@ -308,6 +317,14 @@ class NnueState:
         check(_lib.load().spx_debug_refresh_table_stats(self._h, out.ctypes.data))
         return {"rebuilt": int(out[0]), "served": int(out[1]), "rows_applied": int(out[2]), "scratch_rows": int(out[3])}
 
+    def selfplay_search_stats(self):
+        """spx_debug_selfplay_search_stats: the last searching self-play run of this context split into main-search and
+        quiescence nodes, with the children / candidates evaluated for each kind."""
+        out = np.zeros(4, dtype=np.uint64)
+        check(_lib.load().spx_debug_selfplay_search_stats(self._h, out.ctypes.data))
+        return {"main_nodes": int(out[0]), "quiesce_nodes": int(out[1]), "main_children": int(out[2]),
+                "quiesce_candidates": int(out[3])}
+
     def reset(self, positions, slots):
         """NnueState::reset for each (position, slot): full refresh into the arena."""
         pos = np.ascontiguousarray(positions, dtype=PACKED_DTYPE)
@@ -364,15 +381,17 @@ class NnueState:
         return out
 
     def selfplay(self, n_games, target_games, out_path=None, max_plies=300, dfrc=False, temperature_cp=30, seed=1,
-                 host_threads=0, host_movegen=False, search_nodes=0, refresh_tables=False):
+                 host_threads=0, host_movegen=False, search_nodes=0, refresh_tables=False, quiesce_plies=0):
         """Batched self-play (config 4 shape); returns the stats dict. See spx_selfplay_run.
         host_movegen=True generates moves with the host chess core instead of the device kernel.
         refresh_tables=True: one refresh table per seat (SPX_SELFPLAY_REFRESH_TABLES; device path only, same games).
         search_nodes=k: a live fixed-node search of k expanded nodes picks every move (SPX_SELFPLAY_SEARCH_NODES; 0 = the
-        depth-1 policy; k = 1 plays the same games through the search driver); stats["steps"] then counts expanded nodes."""
+        depth-1 policy; k = 1 plays the same games through the search driver); stats["steps"] then counts expanded nodes.
+        quiesce_plies=q: the search's horizon nodes are quiescence nodes of up to q plies (SPX_SELFPLAY_QUIESCE_PLIES; needs
+        search_nodes >= 2, q <= 8)."""
         params = _lib.SelfplayParams(n_games, target_games, max_plies, 0, int(dfrc), temperature_cp, host_threads,
                                      (1 if host_movegen else 0) | (SELFPLAY_REFRESH_TABLES if refresh_tables else 0)
-                                     | (int(search_nodes) << 8), seed)
+                                     | (int(search_nodes) << 8) | _quiesce_flag(quiesce_plies), seed)
         stats = _lib.SelfplayStats()
         check(_lib.load().spx_selfplay_run(self._h, ctypes.byref(params), out_path.encode() if out_path else None,
                                            ctypes.byref(stats)))
@@ -443,11 +462,13 @@ class DeviceGroup:
         return out
 
     def selfplay(self, n_games, target_games, out_path=None, max_plies=300, dfrc=False, temperature_cp=30, seed=1,
-                 search_nodes=0, refresh_tables=False):
+                 search_nodes=0, refresh_tables=False, quiesce_plies=0):
         """spx_group_selfplay_run: the games dealt to the members, one host thread and one device each; output files
-        <out_path>.<member>.vf; summed stats. refresh_tables: every member its own tables (SPX_SELFPLAY_REFRESH_TABLES)."""
+        <out_path>.<member>.vf; summed stats. refresh_tables: every member its own tables (SPX_SELFPLAY_REFRESH_TABLES).
+        quiesce_plies: SPX_SELFPLAY_QUIESCE_PLIES, as in NnueState.selfplay."""
         params = _lib.SelfplayParams(n_games, target_games, max_plies, 0, int(dfrc), temperature_cp, 0,
-                                     (SELFPLAY_REFRESH_TABLES if refresh_tables else 0) | (int(search_nodes) << 8), seed)
+                                     (SELFPLAY_REFRESH_TABLES if refresh_tables else 0) | (int(search_nodes) << 8)
+                                     | _quiesce_flag(quiesce_plies), seed)
         stats = _lib.SelfplayStats()
         check(_lib.load().spx_group_selfplay_run(self._h, ctypes.byref(params), out_path.encode() if out_path else None,
                                                  ctypes.byref(stats)))
@@ -470,6 +491,14 @@ class DeviceGroup:
 
     def __del__(self):
         self.close()
+
+
+def _quiesce_flag(quiesce_plies):
+    """SPX_SELFPLAY_QUIESCE_PLIES(q) for the four flag bits (the library refuses 9..15 itself)."""
+    q = int(quiesce_plies)
+    if not 0 <= q <= 15:
+        raise ValueError(f"quiesce_plies = {quiesce_plies}: outside 0..15 (the library accepts at most 8)")
+    return q << 4
 
 
 def device_count():

@@ -31,6 +31,9 @@ def main():
     ap.add_argument("--host-movegen", action="store_true", help="generate moves with the host chess core instead of on the GPU")
     ap.add_argument("--search-nodes", type=int, default=0,
                     help="live fixed-node search: expansions per search (SPX_SELFPLAY_SEARCH_NODES; 0 = the depth-1 policy)")
+    ap.add_argument("--quiesce-plies", type=int, default=0,
+                    help="quiescence plies at the search's horizon (SPX_SELFPLAY_QUIESCE_PLIES; 0 = none, at most 8; needs "
+                         "--search-nodes >= 2)")
     ap.add_argument("--preset", default="tame")
     ap.add_argument("--net")
     ap.add_argument("--out")
@@ -59,7 +62,7 @@ def main():
     out = f"{args.out}.{group.rank}.vf" if args.out else None
     stats = state.selfplay(args.games, args.target, out_path=out, max_plies=args.max_plies, dfrc=args.dfrc,
                            temperature_cp=args.temperature, seed=args.seed + group.rank, host_threads=args.threads,
-                           host_movegen=args.host_movegen, search_nodes=args.search_nodes)
+                           host_movegen=args.host_movegen, search_nodes=args.search_nodes, quiesce_plies=args.quiesce_plies)
     written = None
     if out and args.format != "viriformat":
         data = open(out, "rb").read()
@@ -87,6 +90,7 @@ def main():
             "policy": ("live fixed-node search, %d expansions (iterative-deepening alpha-beta, leaves = NNUE(child))" % args.search_nodes)
                       if args.search_nodes else
                       "depth-1: score(move) = -NNUE(child), uniform among moves within %d cp of the best" % args.temperature,
+            "quiesce_plies": args.quiesce_plies,
             "nodes_expanded": total["steps"] if args.search_nodes else None,
         }))
     group.close()
