@@ -472,6 +472,10 @@ int spx_movegen_device(spx_ctx* ctx, const void* d_positions, size_t n, const vo
  *      (Position::isNoisy, src/position.cpp:683-689: not castling, and en passant, a promotion to a queen or an occupied
  *      target square - so a quiet promotion yields its queen alone, a capturing one all four pieces). count[i] = the
  *      number of candidates, in_check[i] as above; the candidates keep the relative order of the full generation.
+ *   2  the quiescence set of mode 1; when the side to move is NOT in check, without the candidates that fail spx_see at
+ *      threshold -81 (the reference's qsearchSeeThreshold, tunable.h:378: captures that lose material are never written);
+ *   3  the same with threshold 1 as the filter (only the clearly winning captures: the futility case of qsearch,
+ *      search.cpp:1572-1576). In check, modes 2 and 3 yield every legal move, as mode 1 does.
  *   other values are reserved for later modes; today they behave as 0.
  * What a host that batches its own quiescence search asks for (and what the self-play driver's quiescence nodes use):
  * the move generation and the evaluation of a quiescence node cost its ~15 % noisy moves instead of all ~35. */
@@ -481,9 +485,39 @@ int spx_movegen_modes(spx_ctx* ctx, const spx_packed_pos* positions, const uint8
 int spx_movegen_modes_device(spx_ctx* ctx, const void* d_positions, const void* d_modes, size_t n, const void* d_parent_values,
                              void* d_children, void* d_moves, void* d_parents, void* d_first, void* d_count, void* d_in_check,
                              size_t capacity, void* d_total, void* stream);
+/* The same with two more optional outputs (NULL = not wanted):
+ *   move_flags  one byte per child, parallel to `moves`: bit 0 = spx_see(move, -81), bit 1 = spx_see(move, 1), bit 2 = the move
+ *               is noisy (Position::isNoisy, the predicate of mode 1) - what a host needs to order and prune the candidates;
+ *   pruned      one uint16_t per position: how many candidates the SEE filter of mode 2 / 3 dropped (0 for modes 0 / 1 and in
+ *               check).
+ * Modes 0 and 1 write the children of spx_movegen_modes, byte for byte. */
+int spx_movegen_flags(spx_ctx* ctx, const spx_packed_pos* positions, const uint8_t* modes, size_t n,
+                      const uint32_t* parent_values, spx_packed_pos* children, uint16_t* moves, uint32_t* parents,
+                      uint32_t* first, uint32_t* count, uint8_t* in_check, uint8_t* move_flags, uint16_t* pruned, size_t capacity,
+                      size_t* total);
+int spx_movegen_flags_device(spx_ctx* ctx, const void* d_positions, const void* d_modes, size_t n, const void* d_parent_values,
+                             void* d_children, void* d_moves, void* d_parents, void* d_first, void* d_count, void* d_in_check,
+                             void* d_move_flags, void* d_pruned, size_t capacity, void* d_total, void* stream);
 /* Host chess core, one position: legal moves (<= 256) in viriformat encoding and, if `children` is not NULL, the
  * records after them; *in_check = side to move is in check. The parity reference of spx_movegen. */
 int spx_pos_legal_moves(const spx_packed_pos* pos, uint16_t* moves, spx_packed_pos* children, int* n, int* in_check);
+
+/* ---- static exchange evaluation (the reference's see::see, src/see.cpp:44-132) ----
+ * Does the exchange that `move` starts on its target square gain at least `threshold` for the side to move? Piece values
+ * pawn 97, knight 434, bishop 464, rook 646, queen 1289, king 0 (tunable.h:155-159); each side recaptures with its least
+ * valuable attacker. Castling gains 0, en passant a pawn, a promotion value(promoted) - value(pawn) and goes on with the
+ * promoted piece; pieces pinned in the position before the move (either colour) take part only on the line through their king
+ * and the target square; sliders behind a capturer join in (x-rays); a king does not capture while the other side still has an
+ * attacker. `move` is a viriformat move word as everywhere else and is assumed legal: an illegal one gives an unspecified 0 / 1.
+ *   spx_pos_see     host chess core, one move: *ok = 0 / 1. The parity reference of spx_see.
+ *   spx_see         n independent (position, move, threshold) triples on the device, ok[i] = 0 / 1; _device: resident buffers
+ *                   (records, u16 moves, i32 thresholds, u8 ok), asynchronous on `stream` (NULL = the context's).
+ * Useful for move ordering and pruning in a host that batches its own search; the move generator's modes 2 / 3 and move_flags
+ * (spx_movegen_flags) apply the same function to the moves it generates. */
+int spx_pos_see(const spx_packed_pos* pos, uint16_t move, int32_t threshold, int* ok);
+int spx_see(spx_ctx* ctx, const spx_packed_pos* positions, const uint16_t* moves, const int32_t* thresholds, size_t n, uint8_t* ok);
+int spx_see_device(spx_ctx* ctx, const void* d_positions, const void* d_moves, const void* d_thresholds, size_t n, void* d_ok,
+                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Batched self-play driver (BASELINE config 4 shape; the game loop of src/datagen/datagen.cpp:96-318): n_games concurrent
@@ -521,10 +555,11 @@ typedef struct spx_selfplay_params {
     uint32_t flags;          /* 0 = moves generated on the device; SPX_SELFPLAY_HOST_MOVEGEN = host chess core instead;
                               * | SPX_SELFPLAY_REFRESH_TABLES: one refresh table per seat (device path only);
                               * | SPX_SELFPLAY_SEARCH_NODES(k): a live fixed-node search picks the moves (device path only);
-                              * | SPX_SELFPLAY_QUIESCE_PLIES(q): ... whose horizon nodes are quiescence nodes (k >= 2) */
+                              * | SPX_SELFPLAY_QUIESCE_PLIES(q): ... whose horizon nodes are quiescence nodes (k >= 2);
+                              * | SPX_SELFPLAY_QUIESCE_PRUNING: ... which prune as the reference's qsearch does (q >= 1) */
     uint64_t seed;
 } spx_selfplay_params;
-enum { SPX_SELFPLAY_HOST_MOVEGEN = 1, SPX_SELFPLAY_REFRESH_TABLES = 2 };
+enum { SPX_SELFPLAY_HOST_MOVEGEN = 1, SPX_SELFPLAY_REFRESH_TABLES = 2, SPX_SELFPLAY_QUIESCE_PRUNING = 4 };
 /* SPX_SELFPLAY_REFRESH_TABLES (device-resident driver, depth-1 and search): one refresh table per seat (spx_acc_reserve_refresh_tables;
  * ~134 KiB each), every arena slot of the seat bound to it before any graph capture. Games are byte-identical with and without
  * it. The host move generation path refuses the flag (SPX_ERR_INVALID_ARG). */
@@ -547,11 +582,21 @@ enum { SPX_SELFPLAY_HOST_MOVEGEN = 1, SPX_SELFPLAY_REFRESH_TABLES = 2 };
  *   descending, move word ascending), each worth -quiesce(child, its static evaluation, -beta, -alpha, q - 1), fail-soft,
  *   cut-off at alpha >= beta.
  * The node budget is still looked at only when an iteration ends, so quiescence nodes lengthen a search beyond k the way any
- * overshoot does; stats.steps counts them, stats.evals counts the candidates evaluated. Not part of it (later work): SEE
- * pruning, futility margins, the evasion cap, a transposition table, draw detection inside the tree. q more arena slots per
- * game. SPX_ERR_INVALID_ARG: q > 8; q > 0 with k <= 1 (the depth-1 policy keeps playing the depth-1 games) or with
- * SPX_SELFPLAY_HOST_MOVEGEN. The rules in full are with SearchStepParams in csrc/spx_kernels.h and restated in
- * tests/_qsearch_rules.py. */
+ * overshoot does; stats.steps counts them, stats.evals counts the candidates evaluated. q more arena slots per game.
+ * SPX_SELFPLAY_QUIESCE_PRUNING (needs q >= 1; absent, everything above is as it was) adds what the reference's qsearch prunes
+ * by, with see = spx_see, fut = stand + 142 (qsearchFpMargin) and "loss" = a score below -25000:
+ *   c is expanded through spx_movegen_flags' mode 3 when fut <= max(alpha, stand), else mode 2 - out of check a capture that
+ *   fails see(1) / see(-81) is never generated, updated or evaluated; out of check in mode 3 with a candidate dropped, best =
+ *   max(best, fut). Then per candidate, in the same order, while best is not a loss: out of check with fut <= alpha and not
+ *   see(1): best = max(best, fut) and on to the next; two candidates searched already: stop; in check and the move is quiet:
+ *   next; not see(-81): next. In check the first candidate is always searched (best starts as a loss).
+ * stats.steps / stats.evals keep their meaning, so evals falls with the generator's filter; the two-candidate cap saves
+ * expansions only, since the order stays by static value and needs every candidate's evaluation. No more arena slots. Still
+ * not part of it (later work): the stand-pat interpolation towards beta (standPatFailFirmT), a transposition table,
+ * repetition / draw detection inside the tree, a capture order that would let the cap save evaluations too.
+ * SPX_ERR_INVALID_ARG: q > 8; q > 0 with k <= 1 (the depth-1 policy keeps playing the depth-1 games) or with
+ * SPX_SELFPLAY_HOST_MOVEGEN; SPX_SELFPLAY_QUIESCE_PRUNING without q >= 1. The rules in full are with SearchStepParams in
+ * csrc/spx_kernels.h and restated in tests/_qsearch_rules.py and tests/_qprune_rules.py. */
 #define SPX_SELFPLAY_QUIESCE_PLIES(q) (((uint32_t)(q) & 15u) << 4)
 typedef struct spx_selfplay_stats {
     uint64_t games, positions, evals, steps;

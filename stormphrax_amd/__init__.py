@@ -25,6 +25,7 @@ from .nnue import (  # noqa: F401
     positions_to_mailboxes,
     random_positions,
     random_successors,
+    see,
     synthetic_net_bytes,
     viri_expand,
     viri_to_fen,

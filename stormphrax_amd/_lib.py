@@ -133,6 +133,11 @@ SYMBOLS = {
     "spx_movegen_device": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
     "spx_movegen_modes": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "spx_movegen_modes_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
+    "spx_movegen_flags": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "spx_movegen_flags_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
+    "spx_pos_see": (ctypes.c_int, [_P, ctypes.c_uint16, ctypes.c_int32, ctypes.POINTER(ctypes.c_int)]),
+    "spx_see": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "spx_see_device": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_size_t, _P, _P]),
     "spx_pos_legal_moves": (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "spx_host_alloc": (_P, [ctypes.c_size_t]),
     "spx_host_free": (None, [_P]),

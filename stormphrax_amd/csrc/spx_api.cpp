@@ -2911,12 +2911,33 @@ int spx_movegen_device(spx_ctx* ctx, const void* d_positions, size_t n, const vo
                                     d_count, d_in_check, capacity, d_total, stream);
 }
 
+// Which instantiation of the generator a public call gets: no modes -> the default one; modes the caller's host array shows to be
+// 0 / 1 only, and no flag outputs -> the modes instantiation, as before modes 2 / 3 existed; resident modes (their values are not
+// known here), modes 2 / 3 or the flag outputs -> the SEE one, which covers modes 0-3. The self-play driver chooses for itself.
+static int movegenOnDevice(spx_ctx* ctx, const void* d_positions, const void* d_modes, bool modesAtMostOne, size_t n,
+                           const void* d_parent_values, void* d_children, void* d_moves, void* d_parents, void* d_first, void* d_count,
+                           void* d_in_check, void* d_move_flags, void* d_pruned, size_t capacity, void* d_total, void* stream);
+
 int spx_movegen_modes_device(spx_ctx* ctx, const void* d_positions, const void* d_modes, size_t n, const void* d_parent_values,
                              void* d_children, void* d_moves, void* d_parents, void* d_first, void* d_count, void* d_in_check,
                              size_t capacity, void* d_total, void* stream) {
+    return spx_movegen_flags_device(ctx, d_positions, d_modes, n, d_parent_values, d_children, d_moves, d_parents, d_first, d_count,
+                                    d_in_check, nullptr, nullptr, capacity, d_total, stream);
+}
+
+int spx_movegen_flags_device(spx_ctx* ctx, const void* d_positions, const void* d_modes, size_t n, const void* d_parent_values,
+                             void* d_children, void* d_moves, void* d_parents, void* d_first, void* d_count, void* d_in_check,
+                             void* d_move_flags, void* d_pruned, size_t capacity, void* d_total, void* stream) {
+    return movegenOnDevice(ctx, d_positions, d_modes, false, n, d_parent_values, d_children, d_moves, d_parents, d_first, d_count,
+                           d_in_check, d_move_flags, d_pruned, capacity, d_total, stream);
+}
+
+static int movegenOnDevice(spx_ctx* ctx, const void* d_positions, const void* d_modes, bool modesAtMostOne, size_t n,
+                           const void* d_parent_values, void* d_children, void* d_moves, void* d_parents, void* d_first, void* d_count,
+                           void* d_in_check, void* d_move_flags, void* d_pruned, size_t capacity, void* d_total, void* stream) {
     if (!ctx || (n && (!d_positions || !d_children || !d_moves || !d_parents || !d_first || !d_count || !d_in_check)) ||
         !d_total || n > (1ull << 30) || capacity > 0xFFFFFFFFull) {
-        setError("spx_movegen_device: invalid argument");
+        setError("spx_movegen_device / spx_movegen_modes_device / spx_movegen_flags_device: invalid argument");
         return SPX_ERR_INVALID_ARG;
     }
     SPX_HIP(hipSetDevice(ctx->device));
@@ -2938,7 +2959,15 @@ int spx_movegen_modes_device(spx_ctx* ctx, const void* d_positions, const void* 
     mp.modes = static_cast<const uint8_t*>(d_modes);
     uint32_t blocks = uint32_t((n + 3) / 4);
     if (blocks > ctx->ftGridCap) blocks = ctx->ftGridCap;
-    SPX_HIP(launchMovegen(mp, blocks, s));
+    if ((d_modes && !modesAtMostOne) || d_move_flags || d_pruned) {
+        MovegenSeeParams sp{};
+        sp.gen = mp;
+        sp.moveFlags = static_cast<uint8_t*>(d_move_flags);
+        sp.pruned = static_cast<uint16_t*>(d_pruned);
+        SPX_HIP(launchMovegenSee(sp, blocks, s));
+    } else {
+        SPX_HIP(launchMovegen(mp, blocks, s));
+    }
     return SPX_OK;
 }
 
@@ -2952,6 +2981,14 @@ int spx_movegen(spx_ctx* ctx, const spx_packed_pos* positions, size_t n, const u
 int spx_movegen_modes(spx_ctx* ctx, const spx_packed_pos* positions, const uint8_t* modes, size_t n,
                       const uint32_t* parent_values, spx_packed_pos* children, uint16_t* moves, uint32_t* parents,
                       uint32_t* first, uint32_t* count, uint8_t* in_check, size_t capacity, size_t* total) {
+    return spx_movegen_flags(ctx, positions, modes, n, parent_values, children, moves, parents, first, count, in_check, nullptr,
+                             nullptr, capacity, total);
+}
+
+int spx_movegen_flags(spx_ctx* ctx, const spx_packed_pos* positions, const uint8_t* modes, size_t n,
+                      const uint32_t* parent_values, spx_packed_pos* children, uint16_t* moves, uint32_t* parents,
+                      uint32_t* first, uint32_t* count, uint8_t* in_check, uint8_t* move_flags, uint16_t* pruned, size_t capacity,
+                      size_t* total) {
     if (!ctx || !total || (n && (!positions || !children || !moves || !parents || !first || !count || !in_check))) {
         setError("spx_movegen: null argument");
         return SPX_ERR_INVALID_ARG;
@@ -2982,6 +3019,12 @@ int spx_movegen_modes(spx_ctx* ctx, const spx_packed_pos* positions, const uint8
     void* dCount = scratch.get(n * 4);
     void* dCheck = scratch.get(n);
     void* dTotal = scratch.get(4);
+    void* dFlags = move_flags ? scratch.get(capacity) : nullptr;
+    void* dPruned = pruned ? scratch.get(n * 2) : nullptr;
+    if ((move_flags && !dFlags) || (pruned && !dPruned)) {
+        setError("spx_movegen: out of device memory");
+        return SPX_ERR_HIP;
+    }
     if (!dPos || (parent_values && !dPv) || (modes && !dModes) || !dChildren || !dMoves || !dParents || !dFirst || !dCount || !dCheck || !dTotal) {
         setError("spx_movegen: out of device memory");
         return SPX_ERR_HIP;
@@ -2990,9 +3033,12 @@ int spx_movegen_modes(spx_ctx* ctx, const spx_packed_pos* positions, const uint8
     SPX_HIP(hipMemcpyAsync(dPos, positions, n * 32, hipMemcpyHostToDevice, s));
     if (parent_values) SPX_HIP(hipMemcpyAsync(dPv, parent_values, n * 4, hipMemcpyHostToDevice, s));
     if (modes) SPX_HIP(hipMemcpyAsync(dModes, modes, n, hipMemcpyHostToDevice, s));
-    const int rc = spx_movegen_modes_device(ctx, dPos, dModes, n, dPv, dChildren, dMoves, dParents, dFirst, dCount, dCheck, capacity,
-                                      dTotal, s);
+    bool modesAtMostOne = modes != nullptr;  // (the host array can be looked at: modes 0 / 1 alone keep the kernel they had)
+    for (size_t i = 0; modes && i < n; ++i) modesAtMostOne = modesAtMostOne && modes[i] <= 1;
+    const int rc = movegenOnDevice(ctx, dPos, dModes, modesAtMostOne, n, dPv, dChildren, dMoves, dParents, dFirst, dCount, dCheck,
+                                   dFlags, dPruned, capacity, dTotal, s);
     if (rc != SPX_OK) return rc;
+    if (pruned) SPX_HIP(hipMemcpyAsync(pruned, dPruned, n * 2, hipMemcpyDeviceToHost, s));
     uint32_t produced = 0;
     SPX_HIP(hipMemcpyAsync(&produced, dTotal, 4, hipMemcpyDeviceToHost, s));
     SPX_HIP(hipMemcpyAsync(first, dFirst, n * 4, hipMemcpyDeviceToHost, s));
@@ -3007,7 +3053,90 @@ int spx_movegen_modes(spx_ctx* ctx, const spx_packed_pos* positions, const uint8
     SPX_HIP(hipMemcpy(children, dChildren, size_t(produced) * 32, hipMemcpyDeviceToHost));
     SPX_HIP(hipMemcpy(moves, dMoves, size_t(produced) * 2, hipMemcpyDeviceToHost));
     SPX_HIP(hipMemcpy(parents, dParents, size_t(produced) * 4, hipMemcpyDeviceToHost));
+    if (move_flags) SPX_HIP(hipMemcpy(move_flags, dFlags, size_t(produced), hipMemcpyDeviceToHost));
     return SPX_OK;
+}
+
+// ---- static exchange evaluation ----
+static Move moveFromViriWord(uint16_t v) {  // no legality test: spx_see assumes a legal move
+    Move m{};
+    m.from = uint8_t(v & 63);
+    m.to = uint8_t((v >> 6) & 63);
+    const int type = v >> 14;
+    m.kind = type == 0 ? kNormal : type == 1 ? kEnPassant : type == 2 ? kCastling : kPromotion;
+    m.promo = m.kind == kPromotion ? uint8_t(((v >> 12) & 3) + 1) : 0;
+    return m;
+}
+
+int spx_pos_see(const spx_packed_pos* pos, uint16_t move, int32_t threshold, int* ok) {
+    Board b;
+    if (!pos || !ok) {
+        setError("spx_pos_see: null argument");
+        return SPX_ERR_INVALID_ARG;
+    }
+    if (!unpackBoard(*pos, b)) {
+        setError("spx_pos_see: bad record");
+        return SPX_ERR_BAD_POSITION;
+    }
+    *ok = see(b, moveFromViriWord(move), threshold) ? 1 : 0;
+    return SPX_OK;
+}
+
+int spx_see_device(spx_ctx* ctx, const void* d_positions, const void* d_moves, const void* d_thresholds, size_t n, void* d_ok,
+                   void* stream) {
+    if (!ctx || (n && (!d_positions || !d_moves || !d_thresholds || !d_ok)) || n > (1ull << 30)) {
+        setError("spx_see_device: invalid argument");
+        return SPX_ERR_INVALID_ARG;
+    }
+    if (n == 0) return SPX_OK;
+    SPX_HIP(hipSetDevice(ctx->device));
+    SeeParams sp{};
+    sp.positions = static_cast<const uint64_t*>(d_positions);
+    sp.moves = static_cast<const uint16_t*>(d_moves);
+    sp.thresholds = static_cast<const int32_t*>(d_thresholds);
+    sp.n = uint32_t(n);
+    sp.ok = static_cast<uint8_t*>(d_ok);
+    SPX_HIP(launchSee(sp, stream ? static_cast<hipStream_t>(stream) : ctx->stream));
+    return SPX_OK;
+}
+
+int spx_see(spx_ctx* ctx, const spx_packed_pos* positions, const uint16_t* moves, const int32_t* thresholds, size_t n, uint8_t* ok) {
+    if (!ctx || (n && (!positions || !moves || !thresholds || !ok))) {
+        setError("spx_see: null argument");
+        return SPX_ERR_INVALID_ARG;
+    }
+    if (n == 0) return SPX_OK;
+    SPX_HIP(hipSetDevice(ctx->device));
+    // convenience entry point (tests, tools): device scratch lives for the duration of the call
+    void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[4] = {n * 32, n * 2, n * 4, n};
+    auto release = [&scratch]() {
+        for (void* q : scratch)
+            if (q) (void)hipFree(q);
+    };
+    for (int i = 0; i < 4; ++i) {
+        if (hipMalloc(&scratch[i], std::max<size_t>(bytes[i], 16)) != hipSuccess) {
+            release();
+            setError("spx_see: out of device memory");
+            return SPX_ERR_HIP;
+        }
+    }
+    hipStream_t s = ctx->stream;
+    int rc = SPX_OK;
+    if (hipMemcpyAsync(scratch[0], positions, bytes[0], hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(scratch[1], moves, bytes[1], hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(scratch[2], thresholds, bytes[2], hipMemcpyHostToDevice, s) != hipSuccess) {
+        setError("spx_see: copy to the device failed");
+        rc = SPX_ERR_HIP;
+    }
+    if (rc == SPX_OK) rc = spx_see_device(ctx, scratch[0], scratch[1], scratch[2], n, scratch[3], s);
+    if (rc == SPX_OK && (hipMemcpyAsync(ok, scratch[3], n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                         hipStreamSynchronize(s) != hipSuccess)) {
+        setError("spx_see: copy from the device failed");
+        rc = SPX_ERR_HIP;
+    }
+    release();
+    return rc;
 }
 
 // ---- viriformat game streams (src/datagen/viriformat.cpp:28-63) ----

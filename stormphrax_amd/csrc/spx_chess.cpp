@@ -638,6 +638,99 @@ void generateLegal(const Board& b, std::vector<Move>& out) {
     }
 }
 
+// ---- static exchange evaluation (see::see / see::gain, src/see.cpp:44-132; values tunable.h:155-159, order tunable.cpp:75-88) ----
+namespace {
+constexpr int kSeeValue[7] = {97, 434, 464, 646, 1289, 0, 0};  // by piece type; 6 = no piece
+
+// the whole line (file, rank or diagonal) through two distinct aligned squares, else nothing (rays.h: rayIntersecting)
+uint64_t lineThrough(int a, int c) {
+    if (a == c) return 0;
+    const uint64_t bit = 1ull << c;
+    if (fileMask(a) & bit) return fileMask(a);
+    if (rankMask(a) & bit) return rankMask(a);
+    if (diagMask(a) & bit) return diagMask(a);
+    if (antiMask(a) & bit) return antiMask(a);
+    return 0;
+}
+
+// Position::calcCheckersAndPins (position.cpp:1536-1565): the single piece of colour c between its king and an enemy slider that
+// would otherwise see the king - rays cut by ENEMY pieces only, so two own pieces on a ray pin neither
+uint64_t pinnedOf(const Board& b, int c) {
+    const int ksq = b.kingSq[c], opp = c ^ 1;
+    const uint64_t kbit = 1ull << ksq, oppOcc = b.colour[opp];
+    const uint64_t diag = lineAttacks(oppOcc, kbit, diagMask(ksq)) | lineAttacks(oppOcc, kbit, antiMask(ksq));
+    const uint64_t orth = lineAttacks(oppOcc, kbit, fileMask(ksq)) | lineAttacks(oppOcc, kbit, rankMask(ksq));
+    uint64_t sliders = (diag & (b.pieces[4 | opp] | b.pieces[8 | opp])) | (orth & (b.pieces[6 | opp] | b.pieces[8 | opp]));
+    uint64_t pinned = 0;
+    while (sliders) {
+        const int sq = ctz64(sliders);
+        sliders &= sliders - 1;
+        const int lo = sq < ksq ? sq : ksq, hi = sq < ksq ? ksq : sq;
+        const uint64_t between = lineThrough(sq, ksq) & ((1ull << hi) - 1) & ~((2ull << lo) - 1);
+        const uint64_t own = between & b.colour[c];
+        if (own && !(own & (own - 1))) pinned |= own;
+    }
+    return pinned;
+}
+}  // namespace
+
+bool see(const Board& b, const Move& m, int threshold) {
+    const int colour = b.stm;
+    int score;
+    if (m.kind == kCastling) score = 0;
+    else if (m.kind == kEnPassant) score = kSeeValue[0];
+    else {
+        const int victim = b.mailbox[m.to];
+        score = victim == kNoPiece ? 0 : kSeeValue[victim >> 1];
+        if (m.kind == kPromotion) score += kSeeValue[m.promo] - kSeeValue[0];
+    }
+    score -= threshold;
+    if (score < 0) return false;
+    const int mover = b.mailbox[m.from];
+    int next = m.kind == kPromotion ? m.promo : (mover == kNoPiece ? 6 : mover >> 1);
+    score -= kSeeValue[next];
+    if (score >= 0) return true;
+
+    const int sq = m.to;
+    const uint64_t bit = 1ull << sq;
+    uint64_t occ = b.occ ^ (1ull << m.from) ^ bit;  // (an en-passant victim stays, as in the reference)
+    const uint64_t diagSliders = b.pieces[4] | b.pieces[5] | b.pieces[8] | b.pieces[9];
+    const uint64_t orthSliders = b.pieces[6] | b.pieces[7] | b.pieces[8] | b.pieces[9];
+    // pins of the position BEFORE the move, both colours: a pinned piece takes part only on the line king - target
+    const uint64_t pinned[2] = {pinnedOf(b, 0), pinnedOf(b, 1)};
+    const uint64_t allowed = ~(pinned[0] | pinned[1]) | (pinned[0] & lineThrough(b.kingSq[0], sq)) |
+                             (pinned[1] & lineThrough(b.kingSq[1], sq));
+    auto diagTo = [&](uint64_t o) { return lineAttacks(o, bit, diagMask(sq)) | lineAttacks(o, bit, antiMask(sq)); };
+    auto orthTo = [&](uint64_t o) { return lineAttacks(o, bit, fileMask(sq)) | lineAttacks(o, bit, rankMask(sq)); };
+    uint64_t attackers = (orthTo(occ) & orthSliders) | (diagTo(occ) & diagSliders) | (pawnAttacks(bit, 1) & b.pieces[0]) |
+                         (pawnAttacks(bit, 0) & b.pieces[1]) | (knightAttacks(bit) & (b.pieces[2] | b.pieces[3])) |
+                         (kingAttacksBb(bit) & (b.pieces[10] | b.pieces[11]));
+    attackers &= allowed;
+    int us = colour ^ 1;
+    for (;;) {
+        const uint64_t ours = attackers & b.colour[us];
+        if (!ours) break;
+        for (next = 0; next < 6; ++next) {  // the least valuable attacker; the value order is the type order, king last
+            const uint64_t bb = ours & b.pieces[(next << 1) | us];
+            if (bb) {
+                occ ^= bb & (0 - bb);
+                break;
+            }
+        }
+        if (next == 0 || next == 2 || next == 4) attackers |= diagTo(occ) & diagSliders;  // x-rays behind the capturer
+        if (next == 3 || next == 4) attackers |= orthTo(occ) & orthSliders;
+        attackers &= occ;
+        score = -score - 1 - kSeeValue[next];
+        us ^= 1;
+        if (score >= 0) {
+            // the capturer was the king and the other side still has an attacker: the capture was not possible (see.cpp:122-127)
+            if (next == 5 && (attackers & b.colour[us])) us ^= 1;
+            break;
+        }
+    }
+    return colour != us;
+}
+
 uint64_t perft(const Board& b, int depth) {
     if (depth == 0) return 1;
     std::vector<Move> moves;

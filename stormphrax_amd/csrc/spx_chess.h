@@ -51,6 +51,10 @@ Board dfrcStart(uint32_t whiteIdx, uint32_t blackIdx);  // independent Chess960 
 
 void generateLegal(const Board& b, std::vector<Move>& out);
 void makeMove(Board& b, const Move& m);
+// Static exchange evaluation: does the exchange that `m` (assumed legal) starts on its target square gain at least `threshold`?
+// The reference's see::see (src/see.cpp) with its values, pin restriction, x-rays and king rule; the parity reference of the
+// device version (spx_movegen.hip: seeAtLeast).
+bool see(const Board& b, const Move& m, int threshold);
 uint64_t perft(const Board& b, int depth);
 std::string moveToUci(const Board& b, const Move& m);  // Chess960-style castling (king takes rook)
 bool moveFromUci(const Board& b, const char* uci, Move& out);

@@ -125,6 +125,22 @@ struct MovegenParams {              // spx_movegen_kernel (spx_movegen.hip)
     const uint8_t* modes;           // nullable, [nPositions]: 0 = every legal move; 1 = the quiescence set (every legal move in
                                     // check, else the noisy ones - Position::isNoisy; `count` = the candidates)
 };
+struct MovegenSeeParams {           // spx_movegen_kernel<true, true>, the SEE instantiation (an argument block of its own: the
+    MovegenParams gen;              // other two keep theirs). gen.modes (nullable = all zero) also knows 2 / 3: mode 1 without the
+                                    // candidates that fail see(move, -81) / see(move, 1) when the side to move is not in check
+    uint8_t* moveFlags;             // nullable, [capacity]: see(-81) | see(1) << 1 | noisy << 2 of every child
+    uint16_t* pruned;               // nullable, [nPositions]: candidates the SEE filter dropped
+    bool flagsForModesOnly;         // moveFlags are written for positions of mode >= 1 only (the self-play driver: the children
+                                    // of a main-search node, mode 0, keep whatever the buffer held - nobody reads them)
+};
+
+struct SeeParams {                  // spx_see_kernel (spx_movegen.hip): n independent (position, move, threshold) triples
+    const uint64_t* positions;      // records as u64[4]
+    const uint16_t* moves;          // viriformat move words (assumed legal)
+    const int32_t* thresholds;
+    uint32_t n;
+    uint8_t* ok;                    // [n] 0 / 1
+};
 
 struct PickParams {                 // spx_pick_kernel (spx_movegen.hip): one uniformly random legal move per position
     uint32_t nGames;
@@ -217,8 +233,28 @@ struct GameStepParams {
 //     candidates in order (value descending, move word ascending): x = -quiesce(child, -value(child), -b, -a, ply + 1, q - 1),
 //       fail-soft update, stop at a >= b;  return best
 // Every expansion counts one node; the budget is still looked at only when an iteration ends at the root. Levels per seat:
-// kSearchLevels + Q. NOT here (later work): SEE pruning, futility margins, the "two legal moves then stop" rule of evasions,
-// a transposition table, draw detection inside the tree.
+// kSearchLevels + Q.
+//
+// PRUNED QUIESCENCE (SPX_SELFPLAY_QUIESCE_PRUNING, needs Q >= 1; search.cpp:1451-1640 with see::see, restated in
+// tests/_qprune_rules.py). see(m, t) = the static exchange evaluation of spx_see; fut = stand + 142 (qsearchFpMargin,
+// tunable.h:377); "loss" = a score below -kScoreWin (core.h:718-720). quiesce() becomes
+//     q == 0 -> stand;  stand >= b -> stand                     (unchanged: decided before c is expanded)
+//     expand c for its candidates in generator mode 3 if fut <= max(a, stand), else in mode 2 (MovegenSeeParams: out of check
+//       the noisy moves that pass see(m, 1) / see(m, -81); in check every legal move)
+//     in check, no candidate -> -(kScoreMate - ply);  in check: best = -INF;  else best = stand, a = max(a, stand)
+//     not in check, mode 3, the generator dropped a candidate: best = max(best, fut)              (search.cpp:1572-1576)
+//     searched = 0;  the candidates in order (value descending, move word ascending), for each m:
+//       if best is not a loss:
+//         not in check and fut <= a and not see(m, 1): best = max(best, fut), next candidate      (:1572-1577; a may have risen)
+//         searched >= 2: stop                                                                     (:1579-1581)
+//         in check and m is not noisy: next candidate                                             (:1608-1610)
+//         not see(m, -81): next candidate                                                         (:1583-1585)
+//       searched += 1;  x = -quiesce(child, -value(child), -b, -a, ply + 1, q - 1), fail-soft, stop at a >= b
+//     return best
+// stand is clamped to +-(kScoreWin - 1), so out of check best is never a loss and the cap is "two candidates". The order stays
+// by static value, so every candidate that passes the generator's filter is still evaluated: the cap saves expansions only.
+// NOT here (later work): the stand-pat interpolation towards beta (standPatFailFirmT), a transposition table, draw detection
+// inside the tree, a capture order that would let the cap save evaluations too.
 constexpr uint32_t kSearchLevels = 8;       // frames per seat of the main search: the root (level 0) .. level 7
 constexpr uint32_t kQuiesceMaxPlies = 8;    // most quiescence plies a caller may ask for (levels 8 .. 7 + Q)
 constexpr uint32_t kSearchChildren = 224;   // children kept per frame (the legal maximum is 218)
@@ -256,6 +292,10 @@ struct SearchStepParams {
                                     // quiescence node)
     unsigned long long* quiesceExpansions;  // Q >= 1, [nSeats][3]: the expansions that were quiescence nodes, their candidates,
                                             // the children of all expansions (spx_debug_selfplay_search_stats)
+    // (pruned quiescence: not NULL = the third instantiation; pendingModes then holds 2 / 3 for a quiescence node)
+    const uint8_t* moveFlags;       // this round's batch: MovegenSeeParams::moveFlags, per child
+    const uint16_t* pruned;         // [nSeats] MovegenSeeParams::pruned of every seat's `pending` node
+    uint8_t* frameFlags;            // [nSeats][levels][kSearchChildren] the move flags of the children kept in the frames
 };
 
 struct ViriExpandParams {          // spx_viri_expand_kernel (spx_movegen.hip)
@@ -309,6 +349,8 @@ hipError_t launchUpdate(const UpdateParams& p, uint32_t gridBlocks, bool splitPe
 hipError_t launchUpdateObserved(const UpdateParams& p, uint32_t gridBlocks, hipStream_t stream);
 hipError_t launchUpdateChain(const ChainParams& p, hipStream_t stream);
 hipError_t launchMovegen(const MovegenParams& p, uint32_t gridBlocks, hipStream_t stream);
+hipError_t launchMovegenSee(const MovegenSeeParams& p, uint32_t gridBlocks, hipStream_t stream);
+hipError_t launchSee(const SeeParams& p, hipStream_t stream);
 hipError_t launchViriExpand(const ViriExpandParams& p, hipStream_t stream);
 hipError_t launchPick(const PickParams& p, hipStream_t stream);
 hipError_t launchGameStep(const GameStepParams& p, hipStream_t stream);

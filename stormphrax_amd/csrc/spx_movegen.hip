@@ -55,6 +55,110 @@ __device__ __forceinline__ bool attackedBy(const Sets& s, int sq, int by, uint64
     return orth && ((lineAttacks(occ, bit, fileMask(sq)) | lineAttacks(occ, bit, rankMask(sq))) & orth);
 }
 
+// ---- static exchange evaluation: see::see (src/see.cpp:44-132) restated for one move per lane on the wave-uniform bitboards;
+// the host's see() (spx_chess.cpp) is its parity reference, tests/golden/see.txt.gz the compiled reference's own answers ----
+__device__ __forceinline__ int seeValue(int type) {  // tunable.h:155-159 by piece type; king and "no piece" (>= 5) are worth 0
+    return type == 0 ? 97 : type == 1 ? 434 : type == 2 ? 464 : type == 3 ? 646 : type == 4 ? 1289 : 0;
+}
+__device__ __forceinline__ int typeAt(const Sets& s, int sq) {
+    const uint64_t bit = 1ull << sq;
+    return (s.pawns & bit) ? 0 : (s.knights & bit) ? 1 : (s.bishops & bit) ? 2 : (s.rooks & bit) ? 3 : (s.queens & bit) ? 4
+           : (s.kings & bit) ? 5 : 6;
+}
+// the whole line through two distinct aligned squares, else nothing (rays.h: rayIntersecting)
+__device__ __forceinline__ uint64_t lineThrough(int a, int c) {
+    const uint64_t bit = 1ull << c;
+    uint64_t line = 0;
+    if (fileMask(a) & bit) line = fileMask(a);
+    if (rankMask(a) & bit) line = rankMask(a);
+    if (diagMask(a) & bit) line = diagMask(a);
+    if (antiMask(a) & bit) line = antiMask(a);
+    return a == c ? 0 : line;
+}
+// Position::calcCheckersAndPins (position.cpp:1536-1565) for colour c: the single own piece between the own king and an enemy
+// slider, rays cut by enemy pieces only. A property of the position: computed once per position, not per move.
+__device__ uint64_t seePinnedOf(const Sets& s, int c) {
+    const uint64_t ownOcc = c ? s.white : (s.occ & ~s.white), oppOcc = s.occ & ~ownOcc;
+    const uint64_t king = s.kings & ownOcc;
+    if (!king) return 0;
+    const int ksq = ctz64(king);
+    const uint64_t diag = lineAttacks(oppOcc, king, diagMask(ksq)) | lineAttacks(oppOcc, king, antiMask(ksq));
+    const uint64_t orth = lineAttacks(oppOcc, king, fileMask(ksq)) | lineAttacks(oppOcc, king, rankMask(ksq));
+    uint64_t sliders = ((diag & (s.bishops | s.queens)) | (orth & (s.rooks | s.queens))) & oppOcc;
+    uint64_t pinned = 0;
+    while (sliders) {
+        const int sq = ctz64(sliders);
+        sliders &= sliders - 1;
+        const int lo = sq < ksq ? sq : ksq, hi = sq < ksq ? ksq : sq;
+        const uint64_t own = lineThrough(sq, ksq) & below(hi) & ~((2ull << lo) - 1) & ownOcc;
+        if (own && !(own & (own - 1))) pinned |= own;
+    }
+    return pinned;
+}
+struct SeePins {  // wave-uniform per position
+    uint64_t pinnedBlack, pinnedWhite;
+    int kingBlack, kingWhite;
+};
+__device__ __forceinline__ SeePins seePins(const Sets& s) {
+    SeePins pins;
+    pins.pinnedBlack = seePinnedOf(s, 0);
+    pins.pinnedWhite = seePinnedOf(s, 1);
+    const uint64_t bk = s.kings & s.occ & ~s.white, wk = s.kings & s.white;
+    pins.kingBlack = bk ? ctz64(bk) : 0;
+    pins.kingWhite = wk ? ctz64(wk) : 0;
+    return pins;
+}
+// kind: ChildKind (0 normal, 1 promotion, 2 castling, 3 en passant); moverType: type of the piece on `from` (6 = none)
+__device__ bool seeAtLeast(const Sets& s, const SeePins& pins, int us, int from, int to, int kind, int promoType, int moverType,
+                           int threshold) {
+    int score = kind == 2 ? 0 : kind == 3 ? seeValue(0) : seeValue(typeAt(s, to));
+    if (kind == 1) score += seeValue(promoType) - seeValue(0);
+    score -= threshold;
+    if (score < 0) return false;
+    int next = kind == 1 ? promoType : moverType;
+    score -= seeValue(next);
+    if (score >= 0) return true;
+
+    const uint64_t bit = 1ull << to;
+    uint64_t occ = s.occ ^ (1ull << from) ^ bit;  // (an en-passant victim stays, as in the reference)
+    const uint64_t diagSliders = s.bishops | s.queens, orthSliders = s.rooks | s.queens;
+    const uint64_t allowed = ~(pins.pinnedBlack | pins.pinnedWhite) | (pins.pinnedBlack & lineThrough(pins.kingBlack, to)) |
+                             (pins.pinnedWhite & lineThrough(pins.kingWhite, to));
+    const uint64_t dMask = diagMask(to), aMask = antiMask(to), fMask = fileMask(to), rMask = rankMask(to);
+    uint64_t attackers = ((lineAttacks(occ, bit, fMask) | lineAttacks(occ, bit, rMask)) & orthSliders) |
+                         ((lineAttacks(occ, bit, dMask) | lineAttacks(occ, bit, aMask)) & diagSliders) |
+                         (pawnAttacks(bit, 1) & s.pawns & ~s.white) | (pawnAttacks(bit, 0) & s.pawns & s.white) |
+                         (knightAttacks(bit) & s.knights) | (kingAttacksBb(bit) & s.kings);
+    attackers &= allowed;
+    int side = us ^ 1;
+    for (int guard = 0; guard < 34; ++guard) {  // (every round takes one piece out of occ: at most 32 rounds)
+        const uint64_t ours = attackers & (side ? s.white : ~s.white);
+        if (!ours) break;
+        // the least valuable attacker: the value order is the type order, king last (tunable.cpp:75-88)
+        uint64_t bb = ours & s.pawns;
+        next = 0;
+        if (!bb) { bb = ours & s.knights; next = 1; }
+        if (!bb) { bb = ours & s.bishops; next = 2; }
+        if (!bb) { bb = ours & s.rooks; next = 3; }
+        if (!bb) { bb = ours & s.queens; next = 4; }
+        if (!bb) { bb = ours & s.kings; next = 5; }
+        occ ^= bb & (0 - bb);
+        if (next == 0 || next == 2 || next == 4) {  // x-rays behind the capturer
+            attackers |= (lineAttacks(occ, bit, dMask) | lineAttacks(occ, bit, aMask)) & diagSliders;
+        }
+        if (next == 3 || next == 4) attackers |= (lineAttacks(occ, bit, fMask) | lineAttacks(occ, bit, rMask)) & orthSliders;
+        attackers &= occ;
+        score = -score - 1 - seeValue(next);
+        side ^= 1;
+        if (score >= 0) {
+            // the capturer was the king and the other side still has an attacker: not possible (see.cpp:122-127)
+            if (next == 5 && (attackers & (side ? s.white : ~s.white))) side ^= 1;
+            break;
+        }
+    }
+    return us != side;
+}
+
 // ---- the 32-nibble piece array (one nibble per occupied square, in square order) as a 128-bit integer ----
 __device__ __forceinline__ u128 nibMask(int idx) {  // the low idx nibbles
     return idx >= 32 ? ~u128(0) : ((u128(1) << (4 * idx)) - 1);
@@ -176,9 +280,35 @@ constexpr int kMaxItems = 256;  // pseudo-legal moves of one position (the legal
 // queen promotion or an occupied target square; an under-promotion only when it captures). The legal flag of every other
 // item is dropped before counting and placement, so the candidates keep the relative order of the full generation. The
 // default instantiation (kModes = false) is the kernel without any of this.
-template <bool kModes>
-__global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
+//
+// kSee (a third instantiation; implies kModes, with modes = NULL read as all zero): the static exchange evaluation of every
+// candidate, next to its legality test. Modes 2 / 3 are mode 1 with one more filter when the side to move is not in check - a
+// candidate that fails see(move, -81) / see(move, 1) loses its legal flag like a quiet move does, so it is never counted, written,
+// updated or evaluated; MovegenSeeParams::pruned counts them. MovegenSeeParams::moveFlags (optional) receives see(-81) | see(1) << 1 |
+// noisy << 2 of every child written. A promotion item stands for up to four children with an exchange value each, so the
+// per-child bits live in a second LDS list beside the items (sAux: one nibble per promotion piece, queen first: the three
+// flag bits and bit 3 = "this child is written"). The pins are computed once per position, only where a filter or the flags
+// need them. kModes = true without kSee stays the kernel it was: mode 1's register count is not touched.
+// (MovegenSeeParams = MovegenParams + the two outputs: the other two instantiations keep the argument block they had)
+template <bool kSee> struct MovegenArgs { using type = MovegenParams; };
+template <> struct MovegenArgs<true> { using type = MovegenSeeParams; };
+__device__ __forceinline__ const MovegenParams& genOf(const MovegenParams& a) { return a; }
+__device__ __forceinline__ const MovegenParams& genOf(const MovegenSeeParams& a) { return a.gen; }
+__device__ __forceinline__ uint8_t* moveFlagsOf(const MovegenParams&) { return nullptr; }
+__device__ __forceinline__ uint8_t* moveFlagsOf(const MovegenSeeParams& a) { return a.moveFlags; }
+__device__ __forceinline__ uint16_t* prunedOf(const MovegenParams&) { return nullptr; }
+__device__ __forceinline__ uint16_t* prunedOf(const MovegenSeeParams& a) { return a.pruned; }
+__device__ __forceinline__ bool prunedOnlyFlags(const MovegenParams&) { return false; }
+__device__ __forceinline__ bool prunedOnlyFlags(const MovegenSeeParams& a) { return a.flagsForModesOnly; }
+
+template <bool kModes, bool kSee = false>
+__global__ __launch_bounds__(256) void spx_movegen_kernel(typename MovegenArgs<kSee>::type args) {
+    static_assert(kModes || !kSee, "the SEE instantiation reads the modes");
+    const MovegenParams& p = genOf(args);
+    uint8_t* const moveFlags = moveFlagsOf(args);
+    uint16_t* const prunedOut = prunedOf(args);
     __shared__ uint16_t sItems[4][kMaxItems];
+    __shared__ uint16_t sAux[kSee ? 4 : 1][kSee ? kMaxItems : 1];
     const uint32_t lane = laneId();
     const uint32_t wave = threadIdx.x >> 6;
     for (uint32_t it = blockIdx.x * 4 + wave; it < p.nPositions; it += gridDim.x * 4) {
@@ -218,9 +348,24 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
         const int from = int(lane);
         // quiescence set wanted and the side to move not in check: only the noisy moves are candidates (wave-uniform)
         bool noisyOnly = false;
-        if (kModes) {
+        if (kModes && !kSee) {
             const uint32_t mode = uint32_t(__builtin_amdgcn_readfirstlane(int(p.modes[it])));
             noisyOnly = mode == 1u && !attackedBy(s, kingSq, them, s.occ, 0);
+        }
+        // SEE instantiation: seeFilter = candidates that fail see(move, seeThreshold) are dropped (modes 2 / 3, not in check)
+        bool seeFilter = false, wantFlags = false;
+        int seeThreshold = -81;
+        SeePins pins{};
+        uint32_t dropped = 0;
+        if (kSee) {
+            const uint32_t mode = p.modes ? uint32_t(__builtin_amdgcn_readfirstlane(int(p.modes[it]))) : 0u;
+            const bool quiesce = mode >= 1u && mode <= 3u && !attackedBy(s, kingSq, them, s.occ, 0);
+            noisyOnly = quiesce;
+            seeFilter = quiesce && mode >= 2u;
+            seeThreshold = mode == 3u ? 1 : -81;
+            // (the self-play driver reads the flags of quiescence nodes only: its main nodes, mode 0, skip the two exchanges per child)
+            wantFlags = moveFlags != nullptr && !(mode == 0u && prunedOnlyFlags(args));
+            if (seeFilter || wantFlags) pins = seePins(s);
         }
 
         // ---- pseudo-legal targets of this lane's piece (generatePseudo, spx_chess.cpp:249-318) ----
@@ -286,11 +431,34 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
                 bool ok = !attackedBy(s, ksq2, them, occ2, capBit);
                 if (kModes && noisyOnly) ok = ok && (capBit != 0 || isPromo);  // (capBit covers en passant)
                 children = ok ? (isPromo && !(kModes && noisyOnly && capBit == 0) ? 4u : 1u) : 0u;
+                if (kSee) {
+                    // one nibble per child of the item (a promotion: queen, rook, bishop, knight - the order they are written in)
+                    uint32_t aux = 0, lost = 0;
+                    for (uint32_t j = 0; j < children; ++j) {
+                        const int promoType = isPromo ? 4 - int(j) : 0;
+                        const int kind = isPromo ? kChildPromotion : isEp ? kChildEnPassant : kChildNormal;
+                        const bool noisy = capBit != 0 || promoType == 4;
+                        bool see81 = true, see1 = true;
+                        if (wantFlags || (seeFilter && seeThreshold != 1)) see81 = seeAtLeast(s, pins, us, f, to, kind, promoType, fType, -81);
+                        if (wantFlags || (seeFilter && seeThreshold == 1)) see1 = seeAtLeast(s, pins, us, f, to, kind, promoType, fType, 1);
+                        const bool keep = !seeFilter || (seeThreshold == 1 ? see1 : see81);
+                        aux |= ((see81 ? 1u : 0u) | (see1 ? 2u : 0u) | (noisy ? 4u : 0u) | (keep ? 8u : 0u)) << (4 * j);
+                        lost += keep ? 0u : 1u;
+                    }
+                    sAux[wave][i] = uint16_t(aux);
+                    children -= lost;
+                    dropped += lost;
+                    ok = children != 0;
+                }
                 sItems[wave][i] = uint16_t(item | (ok ? 0x1000u : 0u) | (isPromo ? 0x2000u : 0u) | (isEp ? 0x4000u : 0u));
             }
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) children += __shfl_xor(children, off, 64);
             total += children;
+        }
+        if (kSee) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) dropped += __shfl_xor(dropped, off, 64);
         }
         // ---- castling, on the king's lane (spx_chess.cpp:288-317): appended as ready-made legal items ----
         {
@@ -323,6 +491,8 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
                 uint32_t slot = nItems;
                 for (int side = 0; side < 2; ++side) {
                     if (castleOk & (1u << side)) {
+                        // (castling gains 0: see(-81) holds, see(1) does not; quiet; written)
+                        if (kSee) sAux[wave][slot] = uint16_t(0x9u);
                         sItems[wave][slot++] = uint16_t(uint32_t(from) | (uint32_t(castleRook[side]) << 6) | 0x9000u);
                     }
                 }
@@ -339,6 +509,7 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
             p.first[it] = base;
             p.count[it] = total;
             p.inCheck[it] = attackedBy(s, kingSq, them, s.occ, 0) ? 1 : 0;
+            if (kSee && prunedOut) prunedOut[it] = uint16_t(dropped);
         }
         base = __shfl(base, 0, 64);
         if (uint64_t(base) + total > p.capacity) continue;  // the host sees cursor > capacity and reports the overflow
@@ -352,7 +523,9 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
             const bool isPromo = (item & 0x2000u) != 0;
             // a quiet promotion in a quiescence set: the queen alone (it is written first)
             const bool queenOnly = kModes && noisyOnly && isPromo && !((s.occ >> ((item >> 6) & 63u)) & 1);
-            const uint32_t mineCount = legal ? (isPromo && !queenOnly ? 4u : 1u) : 0u;
+            // SEE instantiation: the children of the item that are written (bit 3 of each nibble; a quiet promotion has one nibble)
+            const uint32_t aux = kSee && legal ? uint32_t(sAux[wave][i]) : 0u;
+            const uint32_t mineCount = kSee ? uint32_t(__popc(aux & 0x8888u)) : legal ? (isPromo && !queenOnly ? 4u : 1u) : 0u;
             uint32_t incl = mineCount;
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
@@ -365,14 +538,17 @@ __global__ __launch_bounds__(256) void spx_movegen_kernel(MovegenParams p) {
                 const int f = int(item & 63), to = int((item >> 6) & 63);
                 if (isPromo) {
                     for (int pt = 4; pt >= (queenOnly ? 4 : 1); --pt) {
+                        if (kSee && !((aux >> (4 * (4 - pt) + 3)) & 1u)) continue;
                         writeChild(par, s, f, to, kChildPromotion, pt, p.children + size_t(k) * 4, p.moves + k);
                         p.parents[k] = parentValue;
+                        if (kSee && moveFlags) moveFlags[k] = uint8_t((aux >> (4 * (4 - pt))) & 7u);
                         ++k;
                     }
                 } else {
                     const int kind = (item & 0x8000u) ? kChildCastling : (item & 0x4000u) ? kChildEnPassant : kChildNormal;
                     writeChild(par, s, f, to, kind, 0, p.children + size_t(k) * 4, p.moves + k);
                     p.parents[k] = parentValue;
+                    if (kSee && moveFlags) moveFlags[k] = uint8_t(aux & 7u);
                 }
             }
             done += chunkTotal;
@@ -706,8 +882,20 @@ __device__ __forceinline__ uint32_t packQuiesce(int32_t stand, uint32_t plies) {
     return (uint32_t(stand) & 0xFFFFu) | (plies << 16);
 }
 
-template <bool kQuiesce>
+//
+// kPrune (SPX_SELFPLAY_QUIESCE_PRUNING; a third instantiation, implies kQuiesce): the quiescence node of search.cpp:1451-1640 -
+// the rules are with SearchStepParams. A quiescence frame is expanded in generator mode 3 when its futility value stand + 142 is
+// at or below the alpha it was entered with (then only captures that pass see(move, 1) exist, and `pruned` > 0 lifts best to
+// the futility value), else in mode 2; the mode is derived again from the frame's window when the expansion comes back. The
+// candidates' move_flags are kept beside their values (frameFlags) and tested when a candidate's turn comes, in sorted order: a
+// skipped candidate is marked visited without a round. The frame's check status and the number of candidates searched so far
+// travel in SearchFrame::reserved (bits 22 and 20-21). A child that returns without a round still ends the frame on the spot: the
+// later ones would return without a round too, none above it, and a skipped one changes nothing - out of check best is never
+// below the futility value once alpha has reached it.
+constexpr int32_t kQuiesceFutilityMargin = 142;  // qsearchFpMargin, tunable.h:377
+template <bool kQuiesce, bool kPrune = false>
 __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams sp) {
+    static_assert(kQuiesce || !kPrune, "pruning lives in the quiescence nodes");
     const GameStepParams& p = sp.game;
     const uint32_t levels = kQuiesce ? sp.levels : kSearchLevels;
     const uint32_t lane = laneId();
@@ -725,10 +913,12 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
     uint64_t* fRecords = sp.frameRecords + size_t(g) * levels * kSearchChildren * 4;
     int32_t* fValues = sp.frameValues + size_t(g) * levels * kSearchChildren;
     uint16_t* fWords = sp.frameWords + size_t(g) * levels * kSearchChildren;
+    uint8_t* fFlags = kPrune ? sp.frameFlags + size_t(g) * levels * kSearchChildren : nullptr;
 
     MoveResult mr{kNoOutcome, false, false, 0, 0};
     uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;  // the chosen child when a move is played / the next node when the search goes on
     bool descend = false, quiesceNext = false;
+    uint32_t nextMode = 1;  // generator mode of the quiescence node expanded next
     uint32_t nextLevel = 0;
     if (st.active) {
         const uint32_t count = min(uniform(p.count[g]), kSearchChildren);
@@ -760,6 +950,12 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                 fStand = int32_t(int16_t(packed & 0xFFFFu)), fPlies = (packed >> 16) & 15u;
             }
             const bool quiesceNode = kQuiesce && fDepth == 0;
+            // (kPrune) candidates of the frame searched so far (saturating at 3), and whether its side to move is in check
+            uint32_t fSearched = 0;
+            bool fInCheck = inCheck;
+            // this quiescence node was expanded in mode 3: its futility value is at or below the alpha it was entered with
+            const bool futileNode = kPrune && quiesceNode && !inCheck && fStand + kQuiesceFutilityMargin <= fAlpha;
+            const bool lifted = futileNode && uniform(uint32_t(sp.pruned[g])) != 0;  // ... and the generator dropped a candidate
             if (kQuiesce && lane == 0) {
                 if (quiesceNode) sp.quiesceExpansions[3 * g] += 1, sp.quiesceExpansions[3 * g + 1] += count;
                 sp.quiesceExpansions[3 * g + 2] += count;
@@ -768,11 +964,13 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
             enum { kReturn, kDescend, kPlay } action;
             if (count == 0) {  // (a quiescence node out of check: no candidate - the stand pat; stalemate is not detected)
                 res = inCheck ? -(kSearchMate - int32_t(L)) : (quiesceNode ? fStand : 0);
+                if (kPrune && lifted) res = fStand + kQuiesceFutilityMargin;
                 action = kReturn;
             } else {
                 if (quiesceNode && !inCheck) {  // stand pat (none in check: search.cpp:1513-1516)
                     fBest = fStand;
                     fAlpha = max(fAlpha, fStand);
+                    if (kPrune && lifted) fBest = fStand + kQuiesceFutilityMargin;  // (search.cpp:1572-1576 for the moves dropped)
                 }
                 // the children stay: the root's always (the move played comes from them); with quiescence a depth-1 frame's too
                 if (L == 0 || fDepth >= 2 || kQuiesce) {
@@ -780,6 +978,7 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                         const size_t at = size_t(L) * kSearchChildren + k;
                         fValues[at] = clampStaticEval(-p.evals[lo + k]);
                         fWords[at] = p.moves[lo + k];
+                        if (kPrune && quiesceNode) fFlags[at] = sp.moveFlags[lo + k];  // (only quiescence frames read them)
                         for (int w = 0; w < 4; ++w) fRecords[at * 4 + w] = p.children[size_t(lo + k) * 4 + w];
                     }
                 }
@@ -817,6 +1016,7 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                     if (kQuiesce) {
                         const uint32_t packed = uniform(f.reserved);
                         fStand = int32_t(int16_t(packed & 0xFFFFu)), fPlies = (packed >> 16) & 15u;
+                        if (kPrune) fSearched = (packed >> 20) & 3u, fInCheck = ((packed >> 22) & 1u) != 0;
                     }
                     v0 = f.visited[0], v1 = f.visited[1], v2 = f.visited[2], v3 = f.visited[3];
                     const int32_t v = -res;
@@ -845,6 +1045,11 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                 // search the next child of frame L: the best of the children not yet visited (the previous iteration's choice
                 // first at the root)
                 const bool fromBatch = L == batchLevel;
+                if (kPrune && fDepth == 0 && uint32_t(popc64(v0) + popc64(v1) + popc64(v2) + popc64(v3)) >= fCount) {
+                    res = fBest;  // (every candidate left was skipped)
+                    action = kReturn;
+                    continue;
+                }
                 long long key = INT64_MIN;
                 for (uint32_t k = lane; k < fCount; k += 64) {
                     const uint64_t word = k < 64 ? v0 : (k < 128 ? v1 : (k < 192 ? v2 : v3));
@@ -868,6 +1073,33 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                 }
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) idx = min(idx, uint32_t(__shfl_xor(idx, off, 64)));
+                if (kPrune && fDepth == 0) {  // the candidate's turn has come: the tests of search.cpp:1571-1610, in their order
+                    const uint32_t flag = fromBatch ? sp.moveFlags[lo + idx] : fFlags[size_t(L) * kSearchChildren + idx];
+                    if (fBest >= -kScoreWin) {  // (not a loss)
+                        const int32_t fut = fStand + kQuiesceFutilityMargin;
+                        bool skip = false;
+                        if (!fInCheck && fut <= fAlpha && !(flag & 2u)) {
+                            fBest = max(fBest, fut);
+                            skip = true;
+                        } else if (fSearched >= 2) {
+                            res = fBest;
+                            action = kReturn;
+                            continue;
+                        } else if ((fInCheck && !(flag & 4u)) || !(flag & 1u)) {
+                            skip = true;
+                        }
+                        if (skip) {
+                            const uint64_t bit = 1ull << (idx & 63);
+                            v0 |= idx < 64 ? bit : 0ull;
+                            v1 |= (idx >= 64 && idx < 128) ? bit : 0ull;
+                            v2 |= (idx >= 128 && idx < 192) ? bit : 0ull;
+                            v3 |= idx >= 192 ? bit : 0ull;
+                            action = kDescend;
+                            continue;
+                        }
+                    }
+                    fSearched = min(fSearched + 1u, 3u);
+                }
                 uint32_t childPlies = 0;  // (kQuiesce) quiescence plies left at the child
                 if (kQuiesce && fDepth <= 1) {
                     const int32_t v = int32_t(top >> 16);
@@ -905,6 +1137,7 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                     f.count = fCount, f.depth = fDepth, f.alpha = fAlpha, f.beta = fBeta, f.best = fBest, f.bestIdx = fBestIdx;
                     f.cur = fCur;
                     if (kQuiesce) f.reserved = packQuiesce(fStand, fPlies);
+                    if (kPrune) f.reserved |= (fSearched << 20) | (fInCheck ? 1u << 22 : 0u);
                     f.visited[0] = v0, f.visited[1] = v1, f.visited[2] = v2, f.visited[3] = v3;
                     frames[L] = f;
                     SearchFrame below{};
@@ -915,6 +1148,9 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
                         below.depth = 0, below.reserved = packQuiesce(-v, childPlies);
                     }
                     frames[L + 1] = below;
+                }
+                if (kPrune && quiesceNext) {  // the child's futility value against the alpha it is entered with
+                    nextMode = -int32_t(top >> 16) + kQuiesceFutilityMargin <= -fBeta ? 3u : 2u;
                 }
                 const uint64_t* rec = fromBatch ? p.children + size_t(lo + idx) * 4
                                                 : fRecords + (size_t(L) * kSearchChildren + idx) * 4;
@@ -959,7 +1195,7 @@ __global__ __launch_bounds__(256) void spx_search_step_kernel(SearchStepParams s
         p.updParents[g] = descend ? parentSlot : (mr.moved ? oldSlot : 2u * p.nSeatsTotal);
         p.updChildren[g] = descend ? levelSlot : otherSlot;
         sp.pendingSlots[g] = descend ? levelSlot : otherSlot;
-        if (kQuiesce) sp.pendingModes[g] = descend && quiesceNext ? 1 : 0;
+        if (kQuiesce) sp.pendingModes[g] = descend && quiesceNext ? uint8_t(nextMode) : 0;
         if (newRoot) {
             p.slots[g] = otherSlot;
             SearchFrame root{};
@@ -1109,7 +1345,8 @@ hipError_t launchGameStep(const GameStepParams& p, hipStream_t stream) {
 }
 
 hipError_t launchSearchStep(const SearchStepParams& p, hipStream_t stream) {
-    if (p.quiescePlies) hipLaunchKernelGGL(spx_search_step_kernel<true>, dim3((p.game.nSeats + 3) / 4), dim3(256), 0, stream, p);
+    if (p.quiescePlies && p.moveFlags) hipLaunchKernelGGL((spx_search_step_kernel<true, true>), dim3((p.game.nSeats + 3) / 4), dim3(256), 0, stream, p);
+    else if (p.quiescePlies) hipLaunchKernelGGL(spx_search_step_kernel<true>, dim3((p.game.nSeats + 3) / 4), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(spx_search_step_kernel<false>, dim3((p.game.nSeats + 3) / 4), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
@@ -1122,6 +1359,52 @@ hipError_t launchPick(const PickParams& p, hipStream_t stream) {
 hipError_t launchMovegen(const MovegenParams& p, uint32_t gridBlocks, hipStream_t stream) {
     if (p.modes) hipLaunchKernelGGL(spx_movegen_kernel<true>, dim3(gridBlocks), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(spx_movegen_kernel<false>, dim3(gridBlocks), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launchMovegenSee(const MovegenSeeParams& p, uint32_t gridBlocks, hipStream_t stream) {
+    hipLaunchKernelGGL((spx_movegen_kernel<true, true>), dim3(gridBlocks), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// spx_see: n independent (position, move, threshold) triples, one thread each. The bitboards the generator gets from ballots are
+// built here by walking the record's nibbles; the exchange itself is the generator's seeAtLeast.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void spx_see_kernel(SeeParams p) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= p.n) return;
+    const uint64_t* rec = p.positions + size_t(g) * 4;
+    const uint64_t nibLo = rec[1], nibHi = rec[2];
+    Sets s{};
+    s.occ = rec[0];
+    uint64_t rest = s.occ;
+    for (uint32_t idx = 0; rest && idx < 32; ++idx) {
+        const uint64_t bit = rest & (0 - rest);
+        rest &= rest - 1;
+        const uint32_t nib = uint32_t(((idx < 16 ? nibLo : nibHi) >> ((idx & 15) * 4)) & 0xF);
+        int type = int(nib & 7u);
+        if (type >= 6) type = (type == 6) ? 3 : 0;  // as the generator reads them
+        s.pawns |= type == 0 ? bit : 0;
+        s.knights |= type == 1 ? bit : 0;
+        s.bishops |= type == 2 ? bit : 0;
+        s.rooks |= type == 3 ? bit : 0;
+        s.queens |= type == 4 ? bit : 0;
+        s.kings |= type == 5 ? bit : 0;
+        s.white |= (nib & 8u) ? 0 : bit;
+    }
+    const int us = (uint32_t(rec[3]) & 0x80u) ? 0 : 1;
+    const uint32_t word = p.moves[g];
+    const int from = int(word & 63u), to = int((word >> 6) & 63u);
+    const uint32_t typeBits = word >> 14;  // viriformat: 0 normal, 1 en passant, 2 castling, 3 promotion
+    const int kind = typeBits == 3 ? kChildPromotion : typeBits == 2 ? kChildCastling : typeBits == 1 ? kChildEnPassant : kChildNormal;
+    const int promoType = kind == kChildPromotion ? int((word >> 12) & 3u) + 1 : 0;
+    const SeePins pins = seePins(s);
+    p.ok[g] = seeAtLeast(s, pins, us, from, to, kind, promoType, typeAt(s, from), p.thresholds[g]) ? 1 : 0;
+}
+
+hipError_t launchSee(const SeeParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL(spx_see_kernel, dim3((p.n + 255) / 256), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

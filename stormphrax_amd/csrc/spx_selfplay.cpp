@@ -819,6 +819,7 @@ struct DeviceHalf {
     size_t cap = 0;                  // children per ply
     uint64_t* dChildren = nullptr;
     uint16_t* dMoves = nullptr;
+    uint8_t* dMoveFlags = nullptr;   // pruned quiescence only: the generator's move flags per child
     uint32_t* dParents = nullptr;
     int32_t* dEvals = nullptr;
     uint32_t* dTotal = nullptr;
@@ -857,6 +858,7 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     const bool search = searchNodes != 0;
     const uint32_t quiescePlies = (p->flags >> 4) & 15u;  // SPX_SELFPLAY_QUIESCE_PLIES (checked by spx_selfplay_run)
     const uint32_t levels = kSearchLevels + quiescePlies;  // frames and level slots per seat
+    const bool prune = (p->flags & SPX_SELFPLAY_QUIESCE_PRUNING) != 0;  // (needs quiescePlies >= 1: checked by spx_selfplay_run)
     // two slots per seat (current / next position) + the null slot (+ the search levels below the root)
     int rc = spx_acc_reserve(ctx, size_t(G) * 2 + 1 + (search ? size_t(G) * (levels - 1) : 0));
     if (rc != SPX_OK) return rc;
@@ -948,6 +950,9 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     auto* dExpansions = dev.get<unsigned long long>(search ? G : 0);
     auto* dPendingModes = dev.get<uint8_t>(quiescePlies ? G : 0);
     auto* dQuiesceExpansions = dev.get<unsigned long long>(quiescePlies ? size_t(G) * 3 : 0);
+    // pruned quiescence: the generator's move flags of the children kept in the frames, and its per-node count of dropped candidates
+    auto* dFrameFlags = dev.get<uint8_t>(prune ? frameSlots * kSearchChildren : 0);
+    auto* dPruned = dev.get<uint16_t>(prune ? G : 0);
     std::vector<DeviceHalf> halves(nHalves);
     struct RingCloser {  // the halves' output rings
         std::vector<DeviceHalf>& h;
@@ -959,7 +964,8 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
     } ringCloser{halves};
     bool ok = dPositions && dSlots && dRng && dFirst && dCount && dInCheck && dState && dInitial && dGameMoves && dKeys &&
               dPoolRecords && dPoolSeeds && dCounters && hPoolRecords && hPoolSeeds && hPoolSize && dSeats && dFrames &&
-              dFrameRecords && dFrameValues && dFrameWords && dPending && dPendingSlots && dExpansions && dPendingModes && dQuiesceExpansions;
+              dFrameRecords && dFrameValues && dFrameWords && dPending && dPendingSlots && dExpansions && dPendingModes && dQuiesceExpansions &&
+              dFrameFlags && dPruned;
     for (uint32_t h = 0; h < nHalves && ok; ++h) {
         DeviceHalf& hf = halves[h];
         hf.index = h;
@@ -969,6 +975,7 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
         hf.cap = std::min(size_t(seats) * perSeat, ctxMaxBatch(ctx));
         hf.dChildren = dev.get<uint64_t>(hf.cap * 4);
         hf.dMoves = dev.get<uint16_t>(hf.cap);
+        hf.dMoveFlags = dev.get<uint8_t>(prune ? hf.cap : 0);
         hf.dParents = dev.get<uint32_t>(hf.cap);
         hf.dEvals = dev.get<int32_t>(hf.cap);
         hf.dTotal = dev.get<uint32_t>(1);
@@ -982,7 +989,7 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
              hipMemset(hf.dStreamWords, 0, 8) == hipSuccess &&
              hipHostMalloc(reinterpret_cast<void**>(&hf.hRing), size_t(ringWords) * 4, hipHostMallocMapped) == hipSuccess &&
              hipHostGetDevicePointer(reinterpret_cast<void**>(&hf.dRing), hf.hRing, 0) == hipSuccess;
-        ok = ok && hf.dChildren && hf.dMoves && hf.dParents && hf.dEvals && hf.dTotal && hf.dUpdParents && hf.dUpdChildren &&
+        ok = ok && hf.dChildren && hf.dMoves && hf.dMoveFlags && hf.dParents && hf.dEvals && hf.dTotal && hf.dUpdParents && hf.dUpdChildren &&
              hf.dUpdPositions && hf.hStatus && seats <= ctxMaxBatch(ctx);
     }
     if (!ok) {
@@ -1093,7 +1100,16 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
             mp.cursor = hf.dTotal;
             mp.capacity = uint32_t(hf.cap);
             mp.modes = quiescePlies ? dPendingModes + hf.begin : nullptr;  // (a quiescence node wants its candidates only)
-            SPX_SP_HIP(launchMovegen(mp, (seats + 3) / 4, s));
+            if (prune) {  // modes 2 / 3 for the quiescence nodes, the move flags of every child
+                MovegenSeeParams msp{};
+                msp.gen = mp;
+                msp.moveFlags = hf.dMoveFlags;
+                msp.pruned = dPruned + hf.begin;
+                msp.flagsForModesOnly = true;  // (main-search nodes are expanded in mode 0 and never look at flags)
+                SPX_SP_HIP(launchMovegenSee(msp, (seats + 3) / 4, s));
+            } else {
+                SPX_SP_HIP(launchMovegen(mp, (seats + 3) / 4, s));
+            }
         }
         // eval-only children (child slots NULL): ~35 siblings per seat evaluated, none stored
         r = spx_acc_update_eval_device_counted(ctx, hf.dParents, nullptr, hf.dChildren, hf.dTotal, hf.cap, hf.dEvals, s);
@@ -1145,6 +1161,11 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
             sp.expansions = dExpansions + hf.begin;
             sp.pendingModes = quiescePlies ? dPendingModes + hf.begin : nullptr;
             sp.quiesceExpansions = quiescePlies ? dQuiesceExpansions + size_t(hf.begin) * 3 : nullptr;
+            if (prune) {
+                sp.moveFlags = hf.dMoveFlags;
+                sp.pruned = dPruned + hf.begin;
+                sp.frameFlags = dFrameFlags + size_t(hf.begin) * levels * kSearchChildren;
+            }
             SPX_SP_HIP(launchSearchStep(sp, s));
         } else {
             SPX_SP_HIP(launchGameStep(gp, s));
@@ -1347,7 +1368,8 @@ int runDeviceGames(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_p
 extern "C" int spx_selfplay_run(spx_ctx* ctx, const spx_selfplay_params* p, const char* out_path,
                                 spx_selfplay_stats* stats) {
     if (!ctx || !p || !stats || p->n_games == 0 || p->target_games == 0 ||
-        (p->flags & 0xFFu & ~uint32_t(SPX_SELFPLAY_HOST_MOVEGEN | SPX_SELFPLAY_REFRESH_TABLES | 0xF0u)) ||
+        (p->flags & 0xFFu & ~uint32_t(SPX_SELFPLAY_HOST_MOVEGEN | SPX_SELFPLAY_REFRESH_TABLES | SPX_SELFPLAY_QUIESCE_PRUNING | 0xF0u)) ||
+        ((p->flags & SPX_SELFPLAY_QUIESCE_PRUNING) && ((p->flags >> 4) & 15u) == 0) ||  // pruning lives in the quiescence nodes
         ((p->flags >> 4) & 15u) > kQuiesceMaxPlies ||
         (((p->flags >> 4) & 15u) && ((p->flags >> 8) < 2 || (p->flags & SPX_SELFPLAY_HOST_MOVEGEN))) ||  // quiescence: k >= 2, device
         ((p->flags & SPX_SELFPLAY_HOST_MOVEGEN) && (p->flags >> 8)) ||  // the search lives in the device-resident driver

@@ -30,6 +30,7 @@ PRESETS = {"tame": 0, "wild": 1, "extreme": 2, "realistic": 3}
 DEFAULT_SEED = 20260927
 NO_TABLE = 0xFFFFFFFF          # SPX_NO_TABLE: an unbound arena slot (spx_acc_bind_refresh_tables)
 SELFPLAY_REFRESH_TABLES = 2    # SPX_SELFPLAY_REFRESH_TABLES
+SELFPLAY_QUIESCE_PRUNING = 4   # SPX_SELFPLAY_QUIESCE_PRUNING
 
 
 def synthetic_net_bytes(preset="tame", seed=DEFAULT_SEED):
@@ -206,10 +207,12 @@ class NnueState:
                                       ctypes.byref(games), ctypes.byref(bad)))
         return (out, games.value, bad.value, keep.astype(bool)) if with_filter else (out, games.value, bad.value)
 
-    def movegen(self, positions, parent_values=None, capacity=None, modes=None):
+    def movegen(self, positions, parent_values=None, capacity=None, modes=None, want_flags=False):
         """Legal moves + child records of every position, generated on the device (spx_movegen).
         modes: one byte per position (spx_movegen_modes): 0 = every legal move, 1 = the quiescence set (every legal move in
-        check, else the noisy ones). -> dict(children, moves, parents, first, count, in_check)."""
+        check, else the noisy ones), 2 / 3 = the quiescence set without the candidates that fail see(move, -81) / see(move, 1)
+        when not in check. -> dict(children, moves, parents, first, count, in_check); want_flags (spx_movegen_flags) adds
+        move_flags (per child: see(-81) | see(1) << 1 | noisy << 2) and pruned (per position: candidates the filter dropped)."""
         pos = np.ascontiguousarray(positions, dtype=PACKED_DTYPE)
         n = pos.shape[0]
         capacity = capacity if capacity is not None else 64 * n + 256
@@ -221,6 +224,19 @@ class NnueState:
         in_check = np.zeros(n, dtype=np.uint8)
         pv = None if parent_values is None else np.ascontiguousarray(parent_values, dtype=np.uint32)
         total = ctypes.c_size_t()
+        if want_flags:
+            md = None if modes is None else np.ascontiguousarray(modes, dtype=np.uint8)
+            assert md is None or md.shape == (n,)
+            move_flags = np.zeros(capacity, dtype=np.uint8)
+            pruned = np.zeros(n, dtype=np.uint16)
+            check(_lib.load().spx_movegen_flags(self._h, pos.ctypes.data, None if md is None else md.ctypes.data, n,
+                                                None if pv is None else pv.ctypes.data, children.ctypes.data,
+                                                moves.ctypes.data, parents.ctypes.data, first.ctypes.data, count.ctypes.data,
+                                                in_check.ctypes.data, move_flags.ctypes.data, pruned.ctypes.data, capacity,
+                                                ctypes.byref(total)))
+            t = total.value
+            return {"children": children[:t], "moves": moves[:t], "parents": parents[:t], "first": first, "count": count,
+                    "in_check": in_check.astype(bool), "move_flags": move_flags[:t], "pruned": pruned}
         if modes is None:
             check(_lib.load().spx_movegen(self._h, pos.ctypes.data, n, None if pv is None else pv.ctypes.data,
                                           children.ctypes.data, moves.ctypes.data, parents.ctypes.data, first.ctypes.data,
@@ -235,6 +251,17 @@ class NnueState:
         t = total.value
         return {"children": children[:t], "moves": moves[:t], "parents": parents[:t], "first": first, "count": count,
                 "in_check": in_check.astype(bool)}
+
+    def see(self, positions, moves, thresholds):
+        """Static exchange evaluation on the device (spx_see): one bool per (position, viriformat move word, threshold) triple;
+        a scalar threshold applies to every triple."""
+        pos = np.ascontiguousarray(positions, dtype=PACKED_DTYPE)
+        mv = np.ascontiguousarray(moves, dtype=np.uint16)
+        th = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.int32), mv.shape))
+        assert pos.shape == mv.shape and pos.ndim == 1
+        ok = np.zeros(mv.shape[0], dtype=np.uint8)
+        check(_lib.load().spx_see(self._h, pos.ctypes.data, mv.ctypes.data, th.ctypes.data, mv.shape[0], ok.ctypes.data))
+        return ok.astype(bool)
 
     @property
     def scratch_batch(self):
@@ -381,17 +408,20 @@ class NnueState:
         return out
 
     def selfplay(self, n_games, target_games, out_path=None, max_plies=300, dfrc=False, temperature_cp=30, seed=1,
-                 host_threads=0, host_movegen=False, search_nodes=0, refresh_tables=False, quiesce_plies=0):
+                 host_threads=0, host_movegen=False, search_nodes=0, refresh_tables=False, quiesce_plies=0, quiesce_pruning=False):
         """Batched self-play (config 4 shape); returns the stats dict. See spx_selfplay_run.
         host_movegen=True generates moves with the host chess core instead of the device kernel.
         refresh_tables=True: one refresh table per seat (SPX_SELFPLAY_REFRESH_TABLES; device path only, same games).
         search_nodes=k: a live fixed-node search of k expanded nodes picks every move (SPX_SELFPLAY_SEARCH_NODES; 0 = the
         depth-1 policy; k = 1 plays the same games through the search driver); stats["steps"] then counts expanded nodes.
         quiesce_plies=q: the search's horizon nodes are quiescence nodes of up to q plies (SPX_SELFPLAY_QUIESCE_PLIES; needs
-        search_nodes >= 2, q <= 8)."""
+        search_nodes >= 2, q <= 8). quiesce_pruning=True: the quiescence nodes prune as the reference's qsearch does - captures
+        that lose material by static exchange evaluation, the futility margin, at most two candidates searched
+        (SPX_SELFPLAY_QUIESCE_PRUNING; needs quiesce_plies >= 1)."""
         params = _lib.SelfplayParams(n_games, target_games, max_plies, 0, int(dfrc), temperature_cp, host_threads,
                                      (1 if host_movegen else 0) | (SELFPLAY_REFRESH_TABLES if refresh_tables else 0)
-                                     | (int(search_nodes) << 8) | _quiesce_flag(quiesce_plies), seed)
+                                     | (int(search_nodes) << 8) | _quiesce_flag(quiesce_plies)
+                                     | (SELFPLAY_QUIESCE_PRUNING if quiesce_pruning else 0), seed)
         stats = _lib.SelfplayStats()
         check(_lib.load().spx_selfplay_run(self._h, ctypes.byref(params), out_path.encode() if out_path else None,
                                            ctypes.byref(stats)))
@@ -462,13 +492,13 @@ class DeviceGroup:
         return out
 
     def selfplay(self, n_games, target_games, out_path=None, max_plies=300, dfrc=False, temperature_cp=30, seed=1,
-                 search_nodes=0, refresh_tables=False, quiesce_plies=0):
+                 search_nodes=0, refresh_tables=False, quiesce_plies=0, quiesce_pruning=False):
         """spx_group_selfplay_run: the games dealt to the members, one host thread and one device each; output files
         <out_path>.<member>.vf; summed stats. refresh_tables: every member its own tables (SPX_SELFPLAY_REFRESH_TABLES).
-        quiesce_plies: SPX_SELFPLAY_QUIESCE_PLIES, as in NnueState.selfplay."""
+        quiesce_plies / quiesce_pruning: SPX_SELFPLAY_QUIESCE_PLIES / SPX_SELFPLAY_QUIESCE_PRUNING, as in NnueState.selfplay."""
         params = _lib.SelfplayParams(n_games, target_games, max_plies, 0, int(dfrc), temperature_cp, 0,
                                      (SELFPLAY_REFRESH_TABLES if refresh_tables else 0) | (int(search_nodes) << 8)
-                                     | _quiesce_flag(quiesce_plies), seed)
+                                     | _quiesce_flag(quiesce_plies) | (SELFPLAY_QUIESCE_PRUNING if quiesce_pruning else 0), seed)
         stats = _lib.SelfplayStats()
         check(_lib.load().spx_group_selfplay_run(self._h, ctypes.byref(params), out_path.encode() if out_path else None,
                                                  ctypes.byref(stats)))
@@ -650,6 +680,15 @@ def legal_moves(rec):
     check(_lib.load().spx_pos_legal_moves(rec.ctypes.data, moves.ctypes.data, children.ctypes.data, ctypes.byref(n),
                                           ctypes.byref(chk)))
     return moves[: n.value].copy(), children[: n.value].copy(), bool(chk.value)
+
+
+def see(pos, move, threshold):
+    """Host chess core (spx_pos_see): does the exchange `move` (viriformat move word, assumed legal) starts on its target square
+    gain at least `threshold` for the side to move of the packed record `pos`?"""
+    rec = np.ascontiguousarray(pos, dtype=PACKED_DTYPE).reshape(1)
+    ok = ctypes.c_int()
+    check(_lib.load().spx_pos_see(rec.ctypes.data, int(move), int(threshold), ctypes.byref(ok)))
+    return bool(ok.value)
 
 
 def perft(fen, depth):

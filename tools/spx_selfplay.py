@@ -34,6 +34,9 @@ def main():
     ap.add_argument("--quiesce-plies", type=int, default=0,
                     help="quiescence plies at the search's horizon (SPX_SELFPLAY_QUIESCE_PLIES; 0 = none, at most 8; needs "
                          "--search-nodes >= 2)")
+    ap.add_argument("--quiesce-pruning", action="store_true",
+                    help="prune inside the quiescence nodes: SEE on captures, the futility margin, at most two candidates searched "
+                         "(SPX_SELFPLAY_QUIESCE_PRUNING; needs --quiesce-plies >= 1)")
     ap.add_argument("--preset", default="tame")
     ap.add_argument("--net")
     ap.add_argument("--out")
@@ -62,7 +65,8 @@ def main():
     out = f"{args.out}.{group.rank}.vf" if args.out else None
     stats = state.selfplay(args.games, args.target, out_path=out, max_plies=args.max_plies, dfrc=args.dfrc,
                            temperature_cp=args.temperature, seed=args.seed + group.rank, host_threads=args.threads,
-                           host_movegen=args.host_movegen, search_nodes=args.search_nodes, quiesce_plies=args.quiesce_plies)
+                           host_movegen=args.host_movegen, search_nodes=args.search_nodes, quiesce_plies=args.quiesce_plies,
+                           quiesce_pruning=args.quiesce_pruning)
     written = None
     if out and args.format != "viriformat":
         data = open(out, "rb").read()
@@ -90,7 +94,7 @@ def main():
             "policy": ("live fixed-node search, %d expansions (iterative-deepening alpha-beta, leaves = NNUE(child))" % args.search_nodes)
                       if args.search_nodes else
                       "depth-1: score(move) = -NNUE(child), uniform among moves within %d cp of the best" % args.temperature,
-            "quiesce_plies": args.quiesce_plies,
+            "quiesce_plies": args.quiesce_plies, "quiesce_pruning": args.quiesce_pruning,
             "nodes_expanded": total["steps"] if args.search_nodes else None,
         }))
     group.close()
